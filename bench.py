@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the driver's benchmark contract for the k-mer Bloom filter hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json configs[1], "C2"): per GPU a 2^39-bit (64 GiB) BloomFilter, k=31, h=4, and
@@ -23,9 +23,18 @@ timed with HIP events on the launch stream inside the library (btlbf_set_profili
 
 Extra objects on the JSON line: "roofline" for the kernel with the largest share of the timed region,
 "kernels" with the same figures for every kernel, "model_8d" = the whole insert / query operation
-priced with SURVEY 8d's random-access byte model; "cpu_baseline" = the genuine reference build
-(oracle/_ref, kind "reference") or the C port (oracle/, kind "port") timed on this box's host cores
-over a bounded sample of the same workload (rank 0, N=1 only).
+priced with SURVEY 8d's random-access byte model (all three from the timed steps themselves, N=1 only).
+
+--full adds what takes runs of its own after the timed steps (rank 0, N=1 only): "query_all_miss" and
+"query_mixed_hit_rates" (queries with foreign reads), "random_access_ceiling" (bare random-access
+kernels), "side_configs" (the other BASELINE configurations), and "cpu_baseline" = the genuine reference
+build (oracle/_ref, kind "reference") or the C port (oracle/, kind "port") timed on this box's host cores
+over a bounded sample of the same workload.  A plain run only sets up, warms up, times and reports.
+
+--dump-outputs DIR writes what the last timed step computed (rank 0), before anything else touches it:
+counts.npy (float64: k-mers queried, hits), hits_sample.npy (float32 0/1: the contains() bitmask over every
+window of a fixed, seeded sample of reads), and for N=1 filter_sample.npy (float32: filter bytes from fixed,
+seeded blocks) and filter_summary.npy (float64: popcount, then the btlbf_digest words as 32-bit halves).
 """
 import argparse
 import ctypes as C
@@ -57,8 +66,12 @@ def parse():
                     help="reads per GPU (default: the C2 workload, 100 M)")
     ap.add_argument("--log2-bits", type=int, default=int(os.environ.get("BTLBF_BENCH_LOG2_BITS", LOG2_BITS)),
                     help="log2 of filter bits per GPU (default 39 = 64 GiB)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-side-configs", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the side measurements (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a seeded sample of the last timed step's results to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-side-configs", action="store_true", help="with --full: skip side_configs")
     ap.add_argument("--cpu-reads", type=int, default=2_000_000)
     return ap.parse_args()
 
@@ -350,6 +363,52 @@ def traffic_for(traffic, slot, kmers_per_launch):
     return t.get("bytes_per_launch")
 
 
+# --dump-outputs: which reads and filter blocks are sampled depends only on this seed and the run's sizes
+# (splitmix64, so no RNG library version can move them); 2^15 reads x 150 windows + 256 blocks of 16 KiB,
+# as float32, come to 36 MB
+DUMP_SEED = 42
+DUMP_READS = 1 << 15
+DUMP_BLOCKS, DUMP_BLOCK_BYTES = 256, 16384
+
+
+def _splitmix64(n, salt):
+    import numpy as np
+
+    z = np.arange(n, dtype=np.uint64) + np.uint64(salt * 0x9E3779B97F4A7C15 % 2**64)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def dump_outputs(out_dir, torch, lib, hit_bits, counts, n_reads, flt=None):
+    """what the last timed step handed its caller: the query counts, the contains() bitmask over every window
+    of DUMP_READS sampled reads and, for a one-GPU filter, sampled filter bytes plus popcount and digest"""
+    import numpy as np
+
+    from btl_bloomfilter_amd import _lib
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "counts.npy"), np.asarray(counts, dtype=np.float64))
+    rd = _splitmix64(min(DUMP_READS, n_reads), DUMP_SEED) % np.uint64(n_reads)
+    pos = (rd.astype(np.int64)[:, None] * READ_LEN + np.arange(READ_LEN, dtype=np.int64)).ravel()
+    pos = torch.from_numpy(pos).to(hit_bits.device)
+    byte = hit_bits.view(torch.uint8)[pos >> 3].to(torch.int32)
+    hits = ((byte >> (pos & 7).to(torch.int32)) & 1).to(torch.float32).cpu().numpy()
+    np.save(os.path.join(out_dir, "hits_sample.npy"), hits.reshape(-1, READ_LEN))
+    if flt is None:
+        return
+    bb = min(DUMP_BLOCK_BYTES, flt.localBytes())
+    n_blocks = flt.localBytes() // bb
+    blocks = _splitmix64(min(DUMP_BLOCKS, n_blocks), DUMP_SEED + 1) % np.uint64(n_blocks)
+    buf = np.zeros((len(blocks), bb), np.uint8)
+    for i, b in enumerate(blocks.tolist()):
+        _lib.check(lib.btlbf_download(flt._h, C.c_void_p(buf[i].ctypes.data), b * bb, bb))
+    np.save(os.path.join(out_dir, "filter_sample.npy"), buf.astype(np.float32))
+    s, x = flt.digest()
+    np.save(os.path.join(out_dir, "filter_summary.npy"),
+            np.array([flt.getPop(), s >> 32, s & 0xFFFFFFFF, x >> 32, x & 0xFFFFFFFF], dtype=np.float64))
+
+
 def launcher_command(n_gpus, argv, port=None):
     """the command the driver itself uses for N > 1: one rank per GPU on this node, rendezvous on 127.0.0.1"""
     port = port or int(os.environ.get("MASTER_PORT", 29500 + os.getpid() % 2000))
@@ -423,9 +482,10 @@ def main():
     n_bytes = reads.numel()
     hit_bits = torch.zeros((n_bytes + 63) // 64, dtype=torch.int64, device=dev)
     counts = torch.zeros(2, dtype=torch.int64, device=dev)
-    # second query set (reads nobody inserted: ~all misses), reported next to the headline, not part of it
+    # second query set (reads nobody inserted: ~all misses), reported next to the headline with --full, not part of it
     reads_miss = None
-    if world == 1 and not os.environ.get("BTLBF_BENCH_FORCE_SHARDED") and not os.environ.get("BTLBF_BENCH_NO_MISS"):
+    if args.full and world == 1 and not os.environ.get("BTLBF_BENCH_FORCE_SHARDED") \
+            and not os.environ.get("BTLBF_BENCH_NO_MISS"):
         reads_miss = m.synth_reads_device(43, 0, n_reads, READ_LEN, device=local_rank)
 
     force_sharded = bool(os.environ.get("BTLBF_BENCH_FORCE_SHARDED"))  # exercise the multi-GPU code path on one GPU
@@ -571,6 +631,9 @@ def main():
                         "that model assumes, not that HBM ran above its peak",
                 "insert": {"bytes_per_kmer": BYTES_INSERT, "ms": ins * 1e3, "achieved": a_ins, "frac": a_ins / HBM_PEAK_GBS},
                 "query": {"bytes_per_kmer": BYTES_QUERY, "ms": qry * 1e3, "achieved": a_qry, "frac": a_qry / HBM_PEAK_GBS}}
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, torch, lib, hit_bits, tot_counts, n_reads, flt if single else None)
+        if single and args.full:
             if reads_miss is not None:
                 e0, e1 = ev(), ev()
                 e0.record(stream)

@@ -20,7 +20,7 @@ sq_pass() { # tag, quick_bench arguments...
 }
 case "$1" in
 bench)
-	python3 bench.py > $O/bench.json 2> $O/bench.err
+	python3 bench.py --full > $O/bench.json 2> $O/bench.err
 	(cd /tmp && rocprofv3 --kernel-trace --stats -d $O/prof -o runc -- python3 $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-side-configs > $O/bench_under_rocprof.json 2> $O/prof.err)
 	(cd /tmp && BTLBF_BENCH_NO_MISS=1 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/pmc_f -o runc -- python3 $ROOT/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-side-configs > $O/pmc_f.json 2> $O/pmc_f.err)
 	(cd /tmp && BTLBF_BENCH_NO_MISS=1 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/pmc_w -o runc -- python3 $ROOT/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-side-configs > $O/pmc_w.json 2> $O/pmc_w.err)
