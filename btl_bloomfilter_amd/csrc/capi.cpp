@@ -364,9 +364,6 @@ struct DevBuf {
 			pooled_class = cls;
 		return e;
 	}
-	// an error return with work still queued on the stream: the buffer must not go back to the pool (its next user
-	// would share it with that work) -- freed instead, which synchronises
-	void unpool() { pooled_class = 0; }
 	template <class T>
 	T* as()
 	{
@@ -1533,11 +1530,6 @@ bool plan_segments(uint64_t mloc, PartPlan& pl, uint32_t unit_shift = 3)
 	pl.seg_shift = small;
 	if (((mloc + (1ull << small) - 1) >> small) > 512ull * 1024)
 		pl.seg_shift = small + 1;
-	if (const char* e = getenv("BTLBF_SEG_SHIFT")) { // tuning knob: 19 or 20 (= 64 / 128 KiB segments)
-		const int v = atoi(e);
-		if (v == 19 || v == 20)
-			pl.seg_shift = (uint32_t)v - 3 + unit_shift;
-	}
 	pl.n_seg = (mloc + (1ull << pl.seg_shift) - 1) >> pl.seg_shift;
 	// up to 2^20 segments: pass A x one split pass; up to 2^22 (a 256 GiB bit array and beyond): two split passes
 	// (entries stay 32-bit: 1024 level-0 bins of at most 2^32 positions)
@@ -1605,11 +1597,6 @@ bool plan_splits(PartPlan& pl, uint32_t regions_in_total, uint32_t cus = 256)
 	pl.group_bins = 0;
 	if (pl.n_levels >= 2 && pl.lv[0].bins >= 16) {
 		pl.group_bins = (pl.lv[0].bins + 7) / 8;
-		if (const char* e = getenv("BTLBF_GROUP_BINS")) { // tuning knob: level-0 bins split + applied per launch pair
-			const int v = atoi(e);
-			if (v >= 1 && (uint32_t)v <= pl.lv[0].bins)
-				pl.group_bins = (uint32_t)v;
-		}
 		uint32_t bins_g = pl.group_bins, r_in = regions_in_total;
 		for (int j = 1; j < pl.n_levels; ++j) {
 			pl.lv[j].regions = split_slices(bins_g, r_in, cus);
@@ -1830,8 +1817,7 @@ bool plan_level0(const btlbf_filter* f, PartPlan& pl, double call_probes = 0)
 		// same reduction takes 18.6.  So the bins are made of a whole number of SEGMENTS instead, as many as fill the
 		// geometry's rings (768 segments per bin there, 512 bins); pass B then splits wseg ways.  One split level only.
 		const uint32_t rings = 1u << ceil_log2(l0.bins);
-		static const bool pow2_bins = getenv("BTLBF_POW2_BINS") != nullptr; // diagnostic: the old rule
-		if (l0.bins < rings && b1 <= 10 && !pow2_bins) {
+		if (l0.bins < rings && b1 <= 10) {
 			l0.wseg = (uint32_t)((pl.n_seg + rings - 1) / rings);
 			l0.bins = (uint32_t)((pl.n_seg + l0.wseg - 1) / l0.wseg);
 		}
@@ -1850,7 +1836,7 @@ int part_prepare(btlbf_filter* f, const SeqArgs& base, PartTail* tail, PartPlan&
 	if (!plan_level0(f, pl, call_probes(f, base.len)))
 		return BTLBF_OK;
 	PartLevel& l0 = pl.lv[0];
-	l0.regions = part_hash_regions(f->hp, l0.P, cu_count(f->device)); // pass-A workgroups: one or two per CU
+	l0.regions = cu_count(f->device); // pass-A workgroups: one per CU
 	if (!plan_splits(pl, l0.regions, cu_count(f->device)) || !part_hash_fits(f->hp, l0.P))
 		return BTLBF_OK;
 	*tiling = part_tiling(f->hp, l0.P, base.layout, base.len);
@@ -2426,7 +2412,7 @@ int route_plan(const btlbf_filter* f, uint64_t len, const LayoutParams& lay, uns
 		return fail(BTLBF_EINVAL, "routing supports global filters of at least 2^29 bits (2^26 counters)");
 	rp.shift0 = lw - lb;
 	rp.bins_per_shard = rp.bins / rp.shards_per_window;
-	rp.regions = part_hash_regions(f->hp, rp.bins, cu_count(f->device));
+	rp.regions = cu_count(f->device);
 	const PartTiling tl = part_tiling(f->hp, rp.bins, lay, len);
 	const double entries = (double)tiles_for_caps(tl.n_tiles, rp.regions) * probes_per_tile(f, tl) / rp.n_windows;
 	rp.cap = chunks_for(entries / ((double)rp.bins * rp.regions), 1);

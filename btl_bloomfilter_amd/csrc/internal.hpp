@@ -231,7 +231,6 @@ static inline uint32_t part_late_cap() { return 32768u; }
 PartTiling part_tiling(const HashParams& hp, uint32_t p0, const LayoutParams& lay, uint64_t len);
 bool part_supported(const HashParams& hp); // can pass A hash this configuration (1..8 hashes; spaced seeds: the union list)
 bool part_hash_fits(const HashParams& hp, uint32_t p0);
-uint32_t part_hash_regions(const HashParams& hp, uint32_t p0, uint32_t cus); // pass A workgroups = regions per bin
 hipError_t launch_part_hash(const SeqArgs& a, const PartOut& out, uint32_t bin_shift, const PartSide& sd, int query,
                             hipStream_t s);
 // exact != 0: every entry counts (counter increments), so readers honour the exact entry count of a

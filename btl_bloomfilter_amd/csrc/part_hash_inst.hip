@@ -37,35 +37,25 @@ __device__ __forceinline__ T kernarg_reload(uint32_t byte_off)
 // routing mode, where a.mod describes the GLOBAL filter).
 // WINDOW: the filter object is one shard of a larger filter and keeps only the positions inside its
 // window (a.mod.shard_lo, shard_len); otherwise every probe of a clean window is an entry.
-// SMALL: the two-workgroups-per-CU geometry (partition_core.hpp): 512 threads, tiles of 4096 windows, 64 KiB
-// of rings; otherwise 1024 threads, tiles of 8192 windows, 128 KiB of rings.  a.first_tile / a.n_tiles /
-// a.tiles_per_block are in units of THIS kernel's tile.
-template <int H, bool POW2, bool SPACED, bool QUERY, bool WINDOW, bool SMALL>
-__global__ __launch_bounds__(SMALL ? kPartThreadsS : kPartThreads, SMALL ? 4 : 1) void part_hash_kernel(
-    const SeqArgs a, const PartOut out, const uint32_t bin_shift, const PartSide sd)
+// 1024 threads, tiles of 8192 windows, 128 KiB of rings.
+template <int H, bool POW2, bool SPACED, bool QUERY, bool WINDOW>
+__global__ __launch_bounds__(kPartThreads, 1) void part_hash_kernel(const SeqArgs a, const PartOut out,
+                                                                   const uint32_t bin_shift, const PartSide sd)
 {
-	constexpr int NT = SMALL ? kPartThreadsS : kPartThreads;
+	constexpr int NT = kPartThreads;
 	constexpr int kTile = NT * kPartW;
 	extern __shared__ __attribute__((aligned(16))) uint8_t dyn[];
 	__shared__ SeqShared sh;
 	const uint32_t tid = threadIdx.x;
 	const uint32_t k = a.hp.k;
-	// read grid (internal.hpp PartGrid; never with the small geometry): tiles of rg_reads whole reads
-	const bool grid = !SMALL && a.rg_reads != 0;
+	const bool grid = a.rg_reads != 0; // read grid (internal.hpp PartGrid): tiles of rg_reads whole reads
 	const uint32_t tile_cap = grid ? a.rg_cap : seq_tile_cap(kTile, k);
 	const uint32_t tile_bytes = grid ? a.rg_reads * a.layout.read_len : (uint32_t)kTile; // window starts per tile
 	uint8_t* tile = dyn;
 	uint8_t* spaced_lds = dyn + tile_cap + a.sb_words * 4; // (the overlapped schedule's start bitmap: not used here)
 	uint8_t* part_base = spaced_lds + seq_spaced_bytes(a.hp);
-	PartLds pl{};
-	PartLdsS ps{};
-	if (SMALL) {
-		ps = part_carve_s(part_base, out.P);
-		part_init_s(ps, out.P);
-	} else {
-		pl = part_carve(part_base, out.P);
-		part_init<kPartThreads>(pl, out.P);
-	}
+	const PartLds pl = part_carve(part_base, out.P);
+	part_init<kPartThreads>(pl, out.P);
 	seq_setup_tables<NT, SPACED>(sh, a.hp, spaced_lds);
 
 	uint32_t* words = static_cast<uint32_t*>(a.filter);
@@ -114,13 +104,6 @@ __global__ __launch_bounds__(SMALL ? kPartThreadsS : kPartThreads, SMALL ? 4 : 1
 	StageRaw<kPartW> raw;
 	if (t_begin < t_end)
 		seq_stage_load<NT, kPartW>(raw, a.seq, a.len, k, t_begin * (uint64_t)tile_bytes, span);
-	if (SMALL) {
-		// the first tile's words land here; every later tile's land inside the partition rounds (below), so
-		// the top of the loop never waits on vector memory -- a wait there would sit behind the flush stores
-#pragma unroll
-		for (int q = 0; q < kPartW / 4 + 1; ++q)
-			asm volatile("" : "+v"(raw.w[q]));
-	}
 	for (uint64_t t = t_begin; t < t_end; ++t) {
 		const uint64_t g0 = t * (uint64_t)tile_bytes;
 		STAMP(0);
@@ -205,19 +188,7 @@ __global__ __launch_bounds__(SMALL ? kPartThreadsS : kPartThreads, SMALL ? 4 : 1
 				probes([&](uint64_t hv) { return reduce_mod_big(hv, a.mod); });
 			if (w4 == kWpr - 1) {
 				STAMP(2);
-				if (SMALL) {
-					// the next tile's words (requested at the top of this tile) are pinned in their registers
-					// before each flush issues its stores (in both rounds, so that on no path the compiler
-					// still sees them in flight at the top of the next tile, behind the stores)
-					auto land = [&]() {
-#pragma unroll
-						for (int q = 0; q < kPartW / 4 + 1; ++q)
-							asm volatile("" : "+v"(raw.w[q]));
-					};
-					part_round_s<kWpr * H, WINDOW ? 1 : H>(ps, out, blockIdx.x, bin, val, live, ovf, land STAMP_PASS);
-				}
-				else
-					part_round<kPartThreads, kWpr * H, WINDOW ? 1 : H>(pl, out, 0, blockIdx.x, bin, val, live, ovf STAMP_PASS);
+				part_round<kPartThreads, kWpr * H, WINDOW ? 1 : H>(pl, out, 0, blockIdx.x, bin, val, live, ovf STAMP_PASS);
 			}
 		});
 		if (want_bits && grid) {
@@ -252,10 +223,7 @@ __global__ __launch_bounds__(SMALL ? kPartThreadsS : kPartThreads, SMALL ? 4 : 1
 		}
 		my_valid += __popc(vmask);
 	}
-	if (SMALL)
-		part_finish_s(ps, out, blockIdx.x, ovf);
-	else
-		part_finish<kPartThreads>(pl, out, 0, blockIdx.x, ovf);
+	part_finish<kPartThreads>(pl, out, 0, blockIdx.x, ovf);
 	if (a.counts) {
 		const uint32_t wv = wave_sum(my_valid);
 		if ((tid & 63) == 0 && wv)
@@ -709,13 +677,12 @@ __global__ __launch_bounds__(kPartThreads, 1) void part_hash_ov_kernel(const Seq
 	}
 }
 
-template <int H, bool Q, bool SMALL>
+template <int H, bool Q>
 static hipError_t launch_hash_h(const SeqArgs& a, const PartOut& out, uint32_t bin_shift, const PartSide& sd,
                                 size_t dyn, hipStream_t s)
 {
 	const bool pow2 = a.mod.pow2 != 0, spaced = a.hp.n_seeds > 0;
 	const bool window = a.mod.shard_lo != 0 || a.mod.shard_len != a.mod.size;
-	constexpr int NT = SMALL ? kPartThreadsS : kPartThreads;
 	// the overlapped schedule: 1024 threads and bins that eight waves can own (BTLBF_PART_OVERLAP=0: the plain one)
 	static const bool ov_off = [] {
 		const char* e = getenv("BTLBF_PART_OVERLAP");
@@ -729,24 +696,19 @@ static hipError_t launch_hash_h(const SeqArgs& a, const PartOut& out, uint32_t b
 	constexpr bool kOvH = H <= 4;
 	// (spaced seeds keep the plain schedule: the overlapped kernel runs them, bit-identically, but 9 % slower -- 99.7
 	// against 91.3 ms per 6x10^9 k-mers at BASELINE config 5 -- its registers are full without the seeds' running values)
-#ifdef BTLBF_OV_SPACED
-	constexpr bool kOvSpaced = true;
-#else
-	constexpr bool kOvSpaced = false;
-#endif
 	const bool aux = a.sb_words != 0 || (a.read_mask != nullptr && a.rg_reads != 0); // (see part_hash_ov_kernel)
-	const bool overlapped = !SMALL && kOvH && (!spaced || kOvSpaced) && out.P <= 64u * kOvOwners && !ov_off && sd.late_buf != nullptr &&
+	const bool overlapped = kOvH && !spaced && out.P <= 64u * kOvOwners && !ov_off && sd.late_buf != nullptr &&
 	                        sd.late_cap >= kStageEntries;
 #define BTLBF_PLAUNCH(P, S, W)                                                                                      \
 	do {                                                                                                            \
-		if constexpr (!SMALL && (!S || kOvSpaced) && kOvH) {                                                        \
+		if constexpr (!S && kOvH) {                                                                                 \
 			if (overlapped && aux) {                                                                                \
 				hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&part_hash_ov_kernel<H, P, S, Q, W, true>), \
 				                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);            \
 				if (e != hipSuccess)                                                                                \
 					return e;                                                                                       \
-				hipLaunchKernelGGL((part_hash_ov_kernel<H, P, S, Q, W, true>), dim3(out.regions), dim3(NT), dyn, s, a, out, \
-				                   bin_shift, sd);                                                                  \
+				hipLaunchKernelGGL((part_hash_ov_kernel<H, P, S, Q, W, true>), dim3(out.regions), dim3(kPartThreads), dyn, s, \
+				                   a, out, bin_shift, sd);                                                          \
 				break;                                                                                              \
 			}                                                                                                       \
 			if (overlapped) {                                                                                       \
@@ -754,16 +716,16 @@ static hipError_t launch_hash_h(const SeqArgs& a, const PartOut& out, uint32_t b
 				                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);            \
 				if (e != hipSuccess)                                                                                \
 					return e;                                                                                       \
-				hipLaunchKernelGGL((part_hash_ov_kernel<H, P, S, Q, W, false>), dim3(out.regions), dim3(NT), dyn, s, a, out, \
-				                   bin_shift, sd);                                                                  \
+				hipLaunchKernelGGL((part_hash_ov_kernel<H, P, S, Q, W, false>), dim3(out.regions), dim3(kPartThreads), dyn, s, \
+				                   a, out, bin_shift, sd);                                                          \
 				break;                                                                                              \
 			}                                                                                                       \
 		}                                                                                                           \
-		hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&part_hash_kernel<H, P, S, Q, W, SMALL>),    \
+		hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&part_hash_kernel<H, P, S, Q, W>),           \
 		                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);                    \
 		if (e != hipSuccess)                                                                                        \
 			return e;                                                                                               \
-		hipLaunchKernelGGL((part_hash_kernel<H, P, S, Q, W, SMALL>), dim3(out.regions), dim3(NT), dyn, s, a, out,    \
+		hipLaunchKernelGGL((part_hash_kernel<H, P, S, Q, W>), dim3(out.regions), dim3(kPartThreads), dyn, s, a, out,  \
 		                   bin_shift, sd);                                                                          \
 	} while (0)
 #define BTLBF_PLAUNCH_W(P, S)        \
@@ -790,14 +752,10 @@ static hipError_t launch_hash_h(const SeqArgs& a, const PartOut& out, uint32_t b
 #define BTLBF_CAT2(a, b) a##b
 #define BTLBF_CAT(a, b) BTLBF_CAT2(a, b)
 hipError_t BTLBF_CAT(launch_part_hash_h, BTLBF_PART_H)(const SeqArgs& a, const PartOut& out, uint32_t bin_shift,
-                                                       const PartSide& sd, size_t dyn, int query, int small,
-                                                       hipStream_t s)
+                                                       const PartSide& sd, size_t dyn, int query, hipStream_t s)
 {
-	if (small)
-		return query ? launch_hash_h<BTLBF_PART_H, true, true>(a, out, bin_shift, sd, dyn, s)
-		             : launch_hash_h<BTLBF_PART_H, false, true>(a, out, bin_shift, sd, dyn, s);
-	return query ? launch_hash_h<BTLBF_PART_H, true, false>(a, out, bin_shift, sd, dyn, s)
-	             : launch_hash_h<BTLBF_PART_H, false, false>(a, out, bin_shift, sd, dyn, s);
+	return query ? launch_hash_h<BTLBF_PART_H, true>(a, out, bin_shift, sd, dyn, s)
+	             : launch_hash_h<BTLBF_PART_H, false>(a, out, bin_shift, sd, dyn, s);
 }
 
 #if defined(BTLBF_PHASE_STAMPS) && BTLBF_PART_H == 4

@@ -25,8 +25,6 @@
 // GPU) or appended to a spill list of global positions (multi-GPU routing) -- never dropped.
 #include "partition_core.hpp"
 #include <algorithm>
-#include <cstdlib>
-#include <cstring>
 
 namespace btlbf {
 
@@ -450,47 +448,28 @@ __global__ __launch_bounds__(NT) void part_apply_kernel(uint8_t* filter, uint64_
 }
 
 // ---- launchers -----------------------------------------------------------------------------------
-// How pass A's front end is set up for one (hash configuration, level-0 bins): geometry, whether the
-// positional seed table is used, and the dynamic LDS all of it needs.
+// How pass A's front end is set up for one (hash configuration, level-0 bins): whether the positional seed
+// table is used, and the dynamic LDS all of it needs.
 struct PartFront {
-	bool small = false;  // two 512-thread workgroups per CU (partition_core.hpp)
-	uint32_t nt = kPartThreads;
 	uint32_t use_pos_tab = 0;
 	uint32_t dyn = 0;
 };
 
-// The small geometry is opt-in (BTLBF_PART_GEOM=small): measured on MI355X at C2 it is no faster than one
-// 1024-thread workgroup -- pass A is bound by VALU issue, not by the latencies a second workgroup would
-// hide.
-static bool part_want_small(uint32_t p0)
-{
-	if (p0 < kPartMinBinsS || p0 > kPartMaxBinsS)
-		return false;
-	const char* e = getenv("BTLBF_PART_GEOM");
-	return e && !strcmp(e, "small");
-}
-
 // with the positional seed table if it fits, else without (Horner start-up; spaced seeds cannot do without it)
 static bool part_front(const HashParams& hp_in, uint32_t p0, PartFront& fr, uint32_t tile_lds = 0)
 {
-	for (int geom = part_want_small(p0) ? 1 : 0; geom >= 0; --geom) {
-		fr.small = geom == 1;
-		fr.nt = fr.small ? kPartThreadsS : kPartThreads;
-		const uint32_t rings = fr.small ? part_lds_bytes_s(p0) : part_lds_bytes(p0);
-		const uint32_t budget = fr.small ? kPartLdsBudgetS : kPartLdsBudget;
-		for (int tab = 1; tab >= 0; --tab) {
-			HashParams hp = hp_in;
-			if (!tab) {
-				if (hp.n_seeds || !hp.use_pos_tab)
-					break;
-				hp.use_pos_tab = 0;
-			}
-			const uint32_t dyn = (tile_lds && !fr.small ? tile_lds : seq_tile_cap(fr.nt * kPartW, hp.k)) + seq_spaced_bytes(hp) + rings;
-			if (dyn <= budget) {
-				fr.use_pos_tab = hp.use_pos_tab;
-				fr.dyn = dyn;
-				return true;
-			}
+	for (int tab = 1; tab >= 0; --tab) {
+		HashParams hp = hp_in;
+		if (!tab) {
+			if (hp.n_seeds || !hp.use_pos_tab)
+				break;
+			hp.use_pos_tab = 0;
+		}
+		const uint32_t dyn = (tile_lds ? tile_lds : seq_tile_cap(kPartTile, hp.k)) + seq_spaced_bytes(hp) + part_lds_bytes(p0);
+		if (dyn <= kPartLdsBudget) {
+			fr.use_pos_tab = hp.use_pos_tab;
+			fr.dyn = dyn;
+			return true;
 		}
 	}
 	return false;
@@ -503,25 +482,14 @@ bool part_hash_fits(const HashParams& hp, uint32_t p0)
 	return part_front(hp, p0, fr);
 }
 
-// workgroups (= regions per bin) pass A wants for `cus` compute units
-uint32_t part_hash_regions(const HashParams& hp, uint32_t p0, uint32_t cus)
-{
-	PartFront fr;
-	return part_front(hp, p0, fr) && fr.small ? 2 * cus : cus;
-}
-
-// The read grid for (hash configuration, level-0 bins, layout), if it pays: uniform reads, the 1024-thread
-// geometry, the tile image fits the LDS next to the rings, and the lanes it keeps busy beat plain tiles by 5 %.
-// BTLBF_READ_GRID=0 turns it off (measurements).
+// The read grid for (hash configuration, level-0 bins, layout), if it pays: uniform reads, the tile image fits
+// the LDS next to the rings, and the lanes it keeps busy beat plain tiles by 5 %.
 bool part_read_grid(const HashParams& hp, uint32_t p0, const LayoutParams& lay, PartGrid* g)
 {
 	*g = PartGrid();
 	const uint32_t L = lay.starts ? 0 : lay.read_len, k = hp.k;
-	if (L < 16 || L < k || L > 4096 || part_want_small(p0))
+	if (L < 16 || L < k || L > 4096)
 		return false;
-	if (const char* e = getenv("BTLBF_READ_GRID"))
-		if (!strcmp(e, "0"))
-			return false;
 	const uint32_t wins = L - k + 1, gpr = (wins + 7) / 8;
 	uint32_t step = 8; // reads per tile: a multiple of `step` keeps a tile's window bitmap in whole bytes
 	while (step > 1 && ((uint64_t)(step / 2) * L) % 8 == 0)
@@ -529,11 +497,6 @@ bool part_read_grid(const HashParams& hp, uint32_t p0, const LayoutParams& lay, 
 	// every thread stages kPartW/4+1 words of a tile
 	const uint32_t max_bytes = (kPartW / 4 + 1) * kPartThreads * 4 - 16;
 	uint32_t reads = std::min<uint32_t>(kPartThreads / gpr, max_bytes / L);
-	if (const char* e = getenv("BTLBF_GRID_READS")) { // measurements: fewer reads per tile than fit
-		const uint32_t v = (uint32_t)atoi(e);
-		if (v >= 1 && v < reads)
-			reads = v;
-	}
 	reads -= reads % step;
 	if (reads == 0)
 		return false;
@@ -544,7 +507,7 @@ bool part_read_grid(const HashParams& hp, uint32_t p0, const LayoutParams& lay, 
 	const uint32_t bitmap = ((reads * L / 8 + 15) / 16) * 16; // one bit per window start of the tile
 	const uint32_t cap = ((reads * lpad + k + 8 + 15) / 16) * 16 + 2 * bitmap;
 	PartFront fr, plain;
-	if (!part_front(hp, p0, fr, cap) || fr.small || !part_front(hp, p0, plain) || fr.use_pos_tab != plain.use_pos_tab)
+	if (!part_front(hp, p0, fr, cap) || !part_front(hp, p0, plain) || fr.use_pos_tab != plain.use_pos_tab)
 		return false; // (not at the price of the positional seed table)
 	g->reads = reads;
 	g->gpr = gpr;
@@ -556,9 +519,6 @@ bool part_read_grid(const HashParams& hp, uint32_t p0, const LayoutParams& lay, 
 // how pass A cuts a buffer into tiles; all host-side planning is in these units
 PartTiling part_tiling(const HashParams& hp, uint32_t p0, const LayoutParams& lay, uint64_t len)
 {
-	PartFront fr;
-	if (!part_front(hp, p0, fr))
-		fr = PartFront();
 	PartTiling t;
 	const uint32_t L = lay.starts ? 0 : lay.read_len;
 	PartGrid g;
@@ -568,24 +528,24 @@ PartTiling part_tiling(const HashParams& hp, uint32_t p0, const LayoutParams& la
 		t.windows_per_tile = (double)g.reads * (L - hp.k + 1);
 		return t;
 	}
-	t.tile_bytes = fr.nt * kPartW;
+	t.tile_bytes = kPartTile;
 	t.n_tiles = (len + t.tile_bytes - 1) / t.tile_bytes;
 	t.windows_per_tile = (double)t.tile_bytes * (L ? (L >= hp.k ? (double)(L - hp.k + 1) / L : 0.0) : 1.0);
 	return t;
 }
 
 static hipError_t launch_hash_any(const SeqArgs& a, const PartOut& out, uint32_t bin_shift, const PartSide& sd,
-                                  size_t dyn, int query, int small, hipStream_t s)
+                                  size_t dyn, int query, hipStream_t s)
 {
 	switch (a.hp.h) {
-	case 1: return launch_part_hash_h1(a, out, bin_shift, sd, dyn, query, small, s);
-	case 2: return launch_part_hash_h2(a, out, bin_shift, sd, dyn, query, small, s);
-	case 3: return launch_part_hash_h3(a, out, bin_shift, sd, dyn, query, small, s);
-	case 4: return launch_part_hash_h4(a, out, bin_shift, sd, dyn, query, small, s);
-	case 5: return launch_part_hash_h5(a, out, bin_shift, sd, dyn, query, small, s);
-	case 6: return launch_part_hash_h6(a, out, bin_shift, sd, dyn, query, small, s);
-	case 7: return launch_part_hash_h7(a, out, bin_shift, sd, dyn, query, small, s);
-	case 8: return launch_part_hash_h8(a, out, bin_shift, sd, dyn, query, small, s);
+	case 1: return launch_part_hash_h1(a, out, bin_shift, sd, dyn, query, s);
+	case 2: return launch_part_hash_h2(a, out, bin_shift, sd, dyn, query, s);
+	case 3: return launch_part_hash_h3(a, out, bin_shift, sd, dyn, query, s);
+	case 4: return launch_part_hash_h4(a, out, bin_shift, sd, dyn, query, s);
+	case 5: return launch_part_hash_h5(a, out, bin_shift, sd, dyn, query, s);
+	case 6: return launch_part_hash_h6(a, out, bin_shift, sd, dyn, query, s);
+	case 7: return launch_part_hash_h7(a, out, bin_shift, sd, dyn, query, s);
+	case 8: return launch_part_hash_h8(a, out, bin_shift, sd, dyn, query, s);
 	default: return hipErrorInvalidValue;
 	}
 }
@@ -612,12 +572,11 @@ hipError_t launch_part_hash(const SeqArgs& a_in, const PartOut& out, uint32_t bi
 	// ragged layout: room for the start bitmap of the overlapped schedule behind the tile image, if the LDS has it
 	// without giving up the positional table (part_hash_inst.hip; the plain kernels leave it unused)
 	a.sb_words = 0;
-	if (a.layout.starts && !grid && !part_want_small(out.P)) {
+	if (a.layout.starts && !grid) {
 		PartFront plain;
 		const uint32_t words = ((uint32_t)kPartTile + a.hp.k + 2 + 31) / 32, cap = seq_tile_cap(kPartTile, a.hp.k);
 		const uint32_t sb_bytes = (words * 4 + 15) / 16 * 16;
-		if (part_front(a.hp, out.P, plain) && part_front(a.hp, out.P, fr, cap + sb_bytes) && !fr.small &&
-		    fr.use_pos_tab == plain.use_pos_tab)
+		if (part_front(a.hp, out.P, plain) && part_front(a.hp, out.P, fr, cap + sb_bytes) && fr.use_pos_tab == plain.use_pos_tab)
 			a.sb_words = sb_bytes / 4;
 	}
 	const uint32_t tile_lds = grid ? g.cap : a.sb_words ? seq_tile_cap(kPartTile, a.hp.k) + a.sb_words * 4 : 0;
@@ -626,11 +585,11 @@ hipError_t launch_part_hash(const SeqArgs& a_in, const PartOut& out, uint32_t bi
 		return hipErrorInvalidValue;
 	// spaced seeds: two-base rows for the union list's pairs (seq_core.hpp) where the LDS still has the room -- with 256
 	// level-0 bins it has (3 KB fewer per-bin words than with 512), and nothing else gives way for them
-	if (a.hp.want_pair_rows && !fr.small) {
+	if (a.hp.want_pair_rows) {
 		HashParams with = a.hp;
 		with.n_pair_rows = a.hp.want_pair_rows;
 		PartFront fr2;
-		if (part_front(with, out.P, fr2, tile_lds) && !fr2.small && fr2.use_pos_tab == fr.use_pos_tab) {
+		if (part_front(with, out.P, fr2, tile_lds) && fr2.use_pos_tab == fr.use_pos_tab) {
 			a.hp.n_pair_rows = with.n_pair_rows;
 			fr = fr2;
 		}
@@ -643,7 +602,7 @@ hipError_t launch_part_hash(const SeqArgs& a_in, const PartOut& out, uint32_t bi
 	a.hp.use_pos_tab = fr.use_pos_tab;
 	a.tiles_per_block = (a.n_tiles + out.regions - 1) / out.regions;
 	const size_t dyn = fr.dyn;
-	return launch_hash_any(a, out, bin_shift, sd, dyn, query, fr.small, s);
+	return launch_hash_any(a, out, bin_shift, sd, dyn, query, s);
 }
 
 hipError_t launch_part_split(void* filter, const PartIn& in, uint32_t first_in, uint32_t abs_first, uint32_t n_in_bins,

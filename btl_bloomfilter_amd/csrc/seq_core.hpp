@@ -600,9 +600,6 @@ __device__ __forceinline__ void seq_lane_range(const uint8_t* tile, const SeqSha
 		// four unless the caller's buffer is misaligned, li0 + k rarely is: three aligned words and two byte-wise funnel
 		// shifts (the shift is the same in every lane) instead of one misaligned 8-byte read, which this chip replays
 		st.ob = lds_u64(bp);
-#ifdef BTLBF_IB_UNALIGNED
-		st.ib = lds_u64(bp + k);
-#else
 		{
 			const uint32_t a = li0 + k, sh = a & 3u;
 			const uint32_t* w = reinterpret_cast<const uint32_t*>(tile + (a & ~3u));
@@ -610,7 +607,6 @@ __device__ __forceinline__ void seq_lane_range(const uint8_t* tile, const SeqSha
 			const uint32_t lo = __builtin_amdgcn_alignbyte(d1, d0, sh), hi = __builtin_amdgcn_alignbyte(d2, d1, sh);
 			st.ib = ((uint64_t)hi << 32) | lo;
 		}
-#endif
 		st.first_valid = (uint32_t)st.ob & kBaseValid;
 		st.good = good - (((uint32_t)st.ob / kBaseGood) & 1);
 		st.fh = fh;

@@ -1,10 +1,8 @@
 """diagnostic: HIP-event time of pass A (part_hash_kernel) for one library build.
 
-    BTLBF_LIB=btl_bloomfilter_amd/libbtlbf_<tag>.so [BTLBF_PART_GEOM=large|small] python tools/passa_time.py [reads]
+    BTLBF_LIB=btl_bloomfilter_amd/libbtlbf_<tag>.so python tools/passa_time.py [reads]
 
-BTLBF_PART_OVERLAP=0 times the plain schedule instead of the overlapped one.  A diagnostic build
-(BTLBF_BUILD_TAG=nobar BTLBF_CXXFLAGS=-DBTLBF_EXP_NOBARRIER) leaves out the round barriers of the plain schedule; its
-filters are wrong on purpose, only the time of pass A means anything (profiles/r03/passA_overlap.md)."""
+BTLBF_PART_OVERLAP=0 times the plain schedule instead of the overlapped one."""
 import os
 import sys
 
@@ -33,6 +31,6 @@ for rep in range(3):
     prof = f.getProfile()
 ms, calls = prof["insert_hash"]
 print("   per launch ms: " + "  ".join("%s %.3f" % (k, v[0] / v[1]) for k, v in prof.items() if v[1]))
-print("%-40s geom=%-6s pass A %.2f ms per launch (%d launches, %.2f ms per 1e9 k-mers)" % (
-    os.path.basename(path or "libbtlbf.so"), os.environ.get("BTLBF_PART_GEOM", "auto"), ms / calls, calls,
+print("%-40s pass A %.2f ms per launch (%d launches, %.2f ms per 1e9 k-mers)" % (
+    os.path.basename(path or "libbtlbf.so"), ms / calls, calls,
     ms / (n * (L - 30) / 1e9)))

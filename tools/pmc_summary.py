@@ -34,7 +34,7 @@ def slot_of(name):
 
 
 def is_query(name):
-    # QUERY is the 4th template argument of part_hash[_ov]_kernel<H, POW2, SPACED, QUERY, WINDOW[, SMALL]> and the first
+    # QUERY is the 4th template argument of part_hash[_ov]_kernel<H, POW2, SPACED, QUERY, WINDOW[, AUX]> and the first
     # of part_split_kernel<QUERY> / part_apply_kernel<QUERY, NT>
     args = name[name.find("<") + 1:name.find(">(")] if "<" in name else ""
     parts = [a.strip() for a in args.split(",")]
