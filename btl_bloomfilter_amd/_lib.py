@@ -87,6 +87,23 @@ _PROTOS = {
     "btlbf_rank_words": (C.c_uint64, [_P]),
     "btlbf_rank_download": (C.c_int, [_P, _P]),
     "btlbf_rank_query": (C.c_int, [_P, _P, C.c_uint64, C.c_int, _P, _P, C.c_int, _P]),
+    "btlbf_mibf_create": (C.c_int, [C.POINTER(_P), _P, C.c_uint]),
+    "btlbf_mibf_destroy": (None, [_P]),
+    "btlbf_mibf_size": (C.c_uint64, [_P]),
+    "btlbf_mibf_bits": (C.c_uint64, [_P]),
+    "btlbf_mibf_hash_num": (C.c_uint, [_P]),
+    "btlbf_mibf_kmer_size": (C.c_uint, [_P]),
+    "btlbf_mibf_set_scratch": (C.c_int, [_P, C.c_uint64]),
+    "btlbf_mibf_insert_ids_seqs": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(Layout), _P, C.c_int, _P]),
+    "btlbf_mibf_saturate_seqs": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(Layout), _P, C.c_int, _P, C.c_int, _P]),
+    "btlbf_mibf_query_seqs": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(Layout), C.c_uint, _P, _P, _P, _P, C.c_int, _P]),
+    "btlbf_mibf_stats": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "btlbf_mibf_id_counts": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "btlbf_mibf_download": (C.c_int, [_P, _P]),
+    "btlbf_mibf_upload": (C.c_int, [_P, _P]),
+    "btlbf_mibf_download_counts": (C.c_int, [_P, _P]),
+    "btlbf_mibf_store": (C.c_int, [_P, C.c_char_p]),
+    "btlbf_mibf_load": (C.c_int, [C.POINTER(_P), C.c_char_p, _P, C.c_uint]),
     "btlbf_insert_seqs": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(Layout), C.c_int, C.c_int, C.c_int, _P]),
     "btlbf_contains_seqs": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(Layout), _P, _P, _P, C.c_int, _P]),
     "btlbf_insert_and_check_seqs": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(Layout), _P, _P, _P, C.c_int, _P]),

@@ -18,7 +18,7 @@ HEADERS = ["internal.hpp", "host_internal.hpp", "device_utils.hpp", "seq_core.hp
            os.path.join("..", "..", "include", "btlbf.h")]
 # (object name, source, extra flags): pass A of the partitioned pipeline is one unit per hash count
 UNITS = [("capi", "capi.cpp", []), ("fastx", "fastx.cpp", []), ("seq_kernels", "seq_kernels.hip", []), ("aux_kernels", "aux_kernels.hip", []),
-         ("partition_kernels", "partition_kernels.hip", [])]
+         ("partition_kernels", "partition_kernels.hip", []), ("mibf_kernels", "mibf_kernels.hip", [])]
 UNITS += [("part_hash_h%d" % h, "part_hash_inst.hip", ["-DBTLBF_PART_H=%d" % h]) for h in range(1, 9)]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

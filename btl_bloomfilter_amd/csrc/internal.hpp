@@ -298,4 +298,46 @@ hipError_t launch_rank_query(const uint64_t* il, uint64_t n_bits, const uint64_t
 
 int seq_tile_windows(); // windows per workgroup tile (for host-side sizing)
 
+// multi-index Bloom filter, stages 3-4 (mibf_kernels.hip): the ID array over the rank records of launch_rank_build
+struct MibfArgs {
+	const uint8_t* seq; // device
+	uint64_t len;
+	LayoutParams layout;
+	ModParams mod;
+	HashParams hp;
+	const uint64_t* il; // rank records (9 uint64_t per 512 bits)
+	void* data;         // T[pop]
+	const void* counts_t;
+	const uint32_t* ids; // per sequence (converted to T)
+	uint64_t seq0;       // ids index of the batch's first sequence
+	uint32_t seq_bits;   // MIBF_EMIT: key = rank << seq_bits | sequence
+	uint32_t max_miss;
+	uint64_t tiles_per_block;
+	uint64_t* keys; // MIBF_EMIT: len*h; MIBF_DECIDE: cap_mut mutations (rank, window)
+	uint64_t* vals;
+	uint64_t* sat;  // MIBF_DECIDE: ranks to saturate
+	uint64_t cap_mut, cap_sat;
+	unsigned long long* n_out; // MIBF_DECIDE: {mutations, saturated ranks} (counted past the caps)
+	void* values;              // MIBF_QUERY: len*h T
+	uint8_t* hit_bits;
+	uint8_t* valid_bits;
+	unsigned long long* stat; // {clean, found | matched, mutated, saturated}
+};
+hipError_t launch_mibf_seq(int op, int id_bytes, const MibfArgs& a, hipStream_t s);
+hipError_t mibf_sort_temp_bytes(uint64_t n, size_t* bytes);
+hipError_t mibf_sort_pairs(void* temp, size_t temp_bytes, const uint64_t* k_in, uint64_t* k_out, const uint64_t* v_in,
+                           uint64_t* v_out, uint64_t n, uint32_t end_bit, hipStream_t s);
+hipError_t launch_mibf_insert_apply(int id_bytes, const uint64_t* keys, uint64_t* vals, uint64_t n, uint32_t seq_bits,
+                                    const uint32_t* ids, uint64_t seq0, void* data, void* counts, hipStream_t s);
+hipError_t launch_mibf_mutate_apply(int id_bytes, const uint64_t* keys, const uint64_t* vals, uint64_t n,
+                                    const LayoutParams& lay, const uint32_t* ids, void* data, void* counts, hipStream_t s);
+hipError_t launch_mibf_saturate(int id_bytes, const uint64_t* ranks, uint64_t n, void* data, hipStream_t s);
+hipError_t launch_mibf_serial_saturate(int id_bytes, const uint64_t* rows, const uint64_t* valid, uint64_t len, uint32_t h,
+                                       const ModParams& mod, const uint64_t* il, const LayoutParams& lay,
+                                       const uint32_t* ids, uint64_t seq0, void* data, void* counts,
+                                       unsigned long long* stat, hipStream_t s);
+hipError_t launch_mibf_stats(int id_bytes, const void* data, uint64_t n, unsigned long long* out2, hipStream_t s);
+hipError_t launch_mibf_hist(int id_bytes, const void* data, uint64_t n, uint64_t n_bins, unsigned long long* bins,
+                            hipStream_t s);
+
 } // namespace btlbf

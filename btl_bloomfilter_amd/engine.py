@@ -664,3 +664,156 @@ def fastx_batches(path, k, per_line=False, batch_bytes=0, pageable=True, byte_ra
             yield bases, starts
     finally:
         L.btlbf_fastx_close(r)
+
+
+class MIBloomFilter:
+    """Multi-index Bloom filter over a stage-1 bit filter (btlbf_mibf_*; MIBloomFilter.hpp, MIBFConstructSupport.hpp,
+    MIBFQuerySupport.hpp): an ID array of uint16 (id_bytes=2) or uint32 (id_bytes=4) in HBM, addressed by
+    rank(hash % size).  The stage-1 filter may be closed once this object exists."""
+
+    def __init__(self, stage1_filter, id_bytes=2, _handle=None):
+        self._L = _lib.load()
+        self.id_bytes = int(id_bytes)
+        self.dtype = np.uint16 if self.id_bytes == 2 else np.uint32
+        if _handle is None:
+            h = C.c_void_p()
+            check(self._L.btlbf_mibf_create(C.byref(h), stage1_filter._h, self.id_bytes))
+            _handle = h
+        self._h = _handle
+        self.mask = 1 << (8 * self.id_bytes - 1)
+
+    @classmethod
+    def load(cls, path, bloom, id_bytes=2):
+        """MIBloomFilter(path) (MIBloomFilter.hpp:149-248); the bit vector comes from `bloom` (no .sdsl file)"""
+        L = _lib.load()
+        h = C.c_void_p()
+        check(L.btlbf_mibf_load(C.byref(h), str(path).encode(), bloom._h, int(id_bytes)))
+        return cls(None, id_bytes, _handle=h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.btlbf_mibf_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def getPop(self):
+        return self._L.btlbf_mibf_size(self._h)
+
+    def size(self):
+        return self._L.btlbf_mibf_bits(self._h)
+
+    def getHashNum(self):
+        return self._L.btlbf_mibf_hash_num(self._h)
+
+    def getKmerSize(self):
+        return self._L.btlbf_mibf_kmer_size(self._h)
+
+    def setScratchBudget(self, nbytes):
+        check(self._L.btlbf_mibf_set_scratch(self._h, int(nbytes)))
+
+    def _seq_args(self, seqs, ids, starts, read_len):
+        b = _Buf(seqs)
+        lay, keep = _layout(starts, read_len, b.mem)
+        if ids is None:
+            return b, lay, keep, None
+        if b.mem == DEVICE:
+            import torch
+
+            ib = _Buf(ids.to(torch.int32).contiguous() if ids.dtype != torch.int32 else ids.contiguous())
+        else:
+            ib = _Buf(np.ascontiguousarray(ids, np.uint32), np.uint32)
+        return b, lay, keep, ib
+
+    def insertIDs(self, seqs, ids, starts=None, read_len=0, stream=None):
+        """insertMIBF (MIBFConstructSupport.hpp:109-130) of every sequence with its id, in sequence order"""
+        b, lay, keep, ib = self._seq_args(seqs, ids, starts, read_len)
+        check(self._L.btlbf_mibf_insert_ids_seqs(self._h, b.ptr, b.nbytes, C.byref(lay) if lay else None, ib.ptr, b.mem,
+                                                 _stream_ptr(stream, b.keep)))
+
+    def insertSaturation(self, seqs, ids, starts=None, read_len=0, serial=False, stream=None):
+        """insertSaturation (MIBFConstructSupport.hpp:132-214) -> {clean, found, mutated, saturated}"""
+        b, lay, keep, ib = self._seq_args(seqs, ids, starts, read_len)
+        out = np.zeros(4, np.uint64)
+        if b.mem == DEVICE:
+            import torch
+
+            t = torch.zeros(4, dtype=torch.int64, device=b.keep.device)
+            optr = C.c_void_p(t.data_ptr())
+        else:
+            optr = C.c_void_p(out.ctypes.data)
+        check(self._L.btlbf_mibf_saturate_seqs(self._h, b.ptr, b.nbytes, C.byref(lay) if lay else None, ib.ptr,
+                                               ORDER_SERIAL if serial else ORDER_PARALLEL, optr, b.mem,
+                                               _stream_ptr(stream, b.keep)))
+        if b.mem == DEVICE:
+            out = t.cpu().numpy().astype(np.uint64)
+        return dict(zip(("clean", "found", "mutated", "saturated"), (int(x) for x in out)))
+
+    def query(self, seqs, max_miss=0, starts=None, read_len=0, want_counts=False, stream=None):
+        """getMatchSignature (MIBFQuerySupport.hpp:158-217) of every window -> (values[n, h], match_bits, valid_bits)
+        (+ counts {clean, matched} with want_counts); decode(values) gives (id, saturated)"""
+        b, lay, keep, _ = self._seq_args(seqs, None, starts, read_len)
+        n, h = b.nbytes, self.getHashNum()
+        if b.mem == DEVICE:
+            import torch
+
+            tdt = torch.int16 if self.id_bytes == 2 else torch.int32
+            vals = torch.zeros((n, h), dtype=tdt, device=b.keep.device)
+            hit = torch.zeros((n + 63) // 64, dtype=torch.int64, device=b.keep.device)
+            valid = torch.zeros_like(hit)
+            cnt = torch.zeros(2, dtype=torch.int64, device=b.keep.device)
+            ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        else:
+            vals = np.zeros((max(n, 1), h), self.dtype)
+            hit, valid, cnt = _bitmap(n), _bitmap(n), np.zeros(2, np.uint64)
+            ptr = lambda a: C.c_void_p(a.ctypes.data)  # noqa: E731
+        check(self._L.btlbf_mibf_query_seqs(self._h, b.ptr, n, C.byref(lay) if lay else None, int(max_miss), ptr(vals),
+                                            ptr(hit), ptr(valid), ptr(cnt), b.mem, _stream_ptr(stream, b.keep)))
+        if b.mem != DEVICE:
+            vals = vals[:n]
+        return (vals, hit, valid, cnt) if want_counts else (vals, hit, valid)
+
+    def decode(self, values):
+        """raw T values -> (id, saturated) as the reference's pair (v & antiMask, v > mask)"""
+        v = np.asarray(values).astype(self.dtype)
+        return v & self.dtype(self.mask - 1), v > self.dtype(self.mask)
+
+    def data(self):
+        out = np.zeros(max(self.getPop(), 1), self.dtype)
+        check(self._L.btlbf_mibf_download(self._h, C.c_void_p(out.ctypes.data)))
+        return out[: self.getPop()]
+
+    def upload(self, data):
+        a = np.ascontiguousarray(data, self.dtype)
+        assert a.size == self.getPop()
+        check(self._L.btlbf_mibf_upload(self._h, C.c_void_p(a.ctypes.data)))
+
+    def counts(self):
+        out = np.zeros(max(self.getPop(), 1), self.dtype)
+        check(self._L.btlbf_mibf_download_counts(self._h, C.c_void_p(out.ctypes.data)))
+        return out[: self.getPop()]
+
+    def _stats(self):
+        out = (C.c_uint64 * 3)()
+        check(self._L.btlbf_mibf_stats(self._h, out))
+        return list(out)
+
+    def getPopNonZero(self):
+        return self._stats()[1]
+
+    def getPopSaturated(self):
+        return self._stats()[2]
+
+    def getIDCounts(self, n_ids):
+        """getIDCounts (MIBloomFilter.hpp:539-551) -> (counts[n_ids], saturated total)"""
+        counts = np.zeros(max(int(n_ids), 1), np.uint64)
+        sat = C.c_uint64()
+        check(self._L.btlbf_mibf_id_counts(self._h, C.c_void_p(counts.ctypes.data), int(n_ids), C.byref(sat)))
+        return counts[: int(n_ids)], sat.value
+
+    def store(self, path):
+        check(self._L.btlbf_mibf_store(self._h, str(path).encode()))

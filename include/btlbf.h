@@ -298,6 +298,76 @@ int btlbf_rank_download(const btlbf_rank* r, uint64_t* host_dst);
 int btlbf_rank_query(const btlbf_rank* r, const uint64_t* values, uint64_t n, int values_are_hashes,
                      uint64_t* rank_out, uint8_t* bit_out, int mem, void* stream);
 
+/* ---- multi-index Bloom filter (miBF stages 2-4: MIBloomFilter.hpp, MIBFConstructSupport.hpp) -------------
+ * An ID array data[T; pop] (T = uint16_t or uint32_t: id_bytes 2 or 4) and a counter array counts[T; pop], both
+ * addressed by rank(hash % size) over the rank structure above.  mask = 1 << (bits(T)-1) marks a saturated entry
+ * (MIBloomFilter.hpp:36-37).  Sequences are hashed as by btlbf_hash_seqs: ntHashIterator without seeds,
+ * stHashIterator(seq, seeds, h, 1, k) with seeds; only clean windows count.  ids[] holds one id per sequence of
+ * the layout (uint32_t, converted to T), in the memory space `mem` of the sequence buffer.
+ *  mibf_create    : MIBloomFilter(hashNum, k, bv, seeds) (MIBloomFilter.hpp:122-147) + getEmptyMIBF
+ *                   (MIBFConstructSupport.hpp:92-99): rank structure, data and counts zeroed.  f must be a whole bit
+ *                   filter; with spaced seeds h2 must be 1 (MIBFQuerySupport.hpp:167-168).  1..8 hash values per
+ *                   window.  id_bytes other than 2 / 4: EINVAL before any HIP call.  f may be destroyed afterwards.
+ *  mibf_size      : entries of the ID array (getPop, MIBloomFilter.hpp:571-578); mibf_bits: the bit vector size
+ *                   (size(), :622); mibf_hash_num / mibf_kmer_size: getHashNum / getKmerSize (:531-533).
+ *  mibf_set_scratch : HBM budget of one call's scratch (0 = default 2 GiB).
+ *  mibf_insert_ids_seqs : insertMIBF (MIBFConstructSupport.hpp:109-130), one call per sequence s with id ids[s], in
+ *                   sequence order.  Each sequence's distinct hash values are walked in ASCENDING value order (the
+ *                   reference walks a dense_hash_set in an unspecified order; this rule is this library's):
+ *                   r = rank(v), c = counts[r] = T(counts[r] + 1), x = T(v ^ id); setData(r, id) when c != 0 and
+ *                   x % c == c - 1 (c == 0 is a wrapped counter, UB in the reference: no replacement).  setData
+ *                   (MIBloomFilter.hpp:625-634) keeps the saturation bit iff the old value is > mask.  The result does
+ *                   not depend on how sequences are split into calls or batches.  Needs a layout.
+ *  mibf_saturate_seqs : insertSaturation -> setSatIfMissing (MIBFConstructSupport.hpp:132-214) per clean window:
+ *                   seenSet and replacementIDs start with h zeros; the candidate with the LARGEST count by strict >
+ *                   from 0 wins (the first maximum); mutation = setData then ++counts; fallback = saturate(hashes)
+ *                   (MIBloomFilter.hpp:440-446).  order BTLBF_ORDER_SERIAL: one lane walks sequences and windows in
+ *                   buffer order (the reference's loop, bit for bit).  BTLBF_ORDER_PARALLEL: every window decides
+ *                   against data / counts as they stood at the start of the call; then each mutated position gets
+ *                   counts += its choosers (T wrap) and the id of its last chooser in (sequence, window) order by
+ *                   setData's rule against the start value; then every saturation is ORed in.  A parallel call whose
+ *                   decisions do not fit the scratch budget returns ENOMEM and changes nothing.
+ *                   counts4 (optional, this memory space) = {clean windows, found, mutated, saturated}.
+ *  mibf_query_seqs : getMatchSignature (MIBFQuerySupport.hpp:158-217) over atRank (MIBloomFilter.hpp:478-515):
+ *                   values[len*h] (T, window p at row p): data[rank] at hit positions of a matching window, else 0;
+ *                   match_bits / valid_bits: per-window bitmaps as btlbf_contains_seqs; counts2 = {clean windows,
+ *                   matching windows}.  With seeds a window matches with at most max_miss clear bits; without seeds
+ *                   all h bits are needed and max_miss is ignored.  (id, saturated) = (v & ~mask, v > mask).
+ *  mibf_stats     : out3 = {getPop, getPopNonZero, getPopSaturated (> mask)} (MIBloomFilter.hpp:571-620).
+ *  mibf_id_counts : getIDCounts (MIBloomFilter.hpp:539-551) as a device histogram: counts[n_ids] (host) +=
+ *                   entries per id (v & ~mask when v > mask, else v; ids >= n_ids are not counted);
+ *                   *saturated = entries > mask.
+ *  mibf_download / mibf_upload / mibf_download_counts : the data / counts arrays, size * id_bytes bytes (host).
+ *  mibf_store     : the data file of MIBloomFilter::store (:264-305, writeHeader :722-742), byte for byte: the packed
+ *                   32-byte header {"MIBLOOMF", hlen = 32 + k*n_seeds, size, nhash, kmer, version = 1}, the seeds
+ *                   (k bytes each), data little-endian.  The bit vector is NOT written (no .sdsl companion file):
+ *                   store the stage-1 filter with btlbf_store.
+ *  mibf_load      : MIBloomFilter(path) (:149-248): missing file EIO; wrong magic, hlen, version or a data length
+ *                   other than size * id_bytes EFORMAT -- all before any HIP call.  The bit vector comes from f
+ *                   (same k and hash count as the file); a popcount other than size is EFORMAT. */
+typedef struct btlbf_mibf btlbf_mibf;
+int btlbf_mibf_create(btlbf_mibf** out, btlbf_filter* f, unsigned id_bytes);
+void btlbf_mibf_destroy(btlbf_mibf* m);
+uint64_t btlbf_mibf_size(const btlbf_mibf* m);
+uint64_t btlbf_mibf_bits(const btlbf_mibf* m);
+unsigned btlbf_mibf_hash_num(const btlbf_mibf* m);
+unsigned btlbf_mibf_kmer_size(const btlbf_mibf* m);
+int btlbf_mibf_set_scratch(btlbf_mibf* m, uint64_t bytes);
+int btlbf_mibf_insert_ids_seqs(btlbf_mibf* m, const char* seq, uint64_t len, const btlbf_layout* layout,
+                               const uint32_t* ids, int mem, void* stream);
+int btlbf_mibf_saturate_seqs(btlbf_mibf* m, const char* seq, uint64_t len, const btlbf_layout* layout,
+                             const uint32_t* ids, int order, uint64_t* counts4, int mem, void* stream);
+int btlbf_mibf_query_seqs(btlbf_mibf* m, const char* seq, uint64_t len, const btlbf_layout* layout, unsigned max_miss,
+                          void* values, uint64_t* match_bits, uint64_t* valid_bits, uint64_t* counts2, int mem,
+                          void* stream);
+int btlbf_mibf_stats(btlbf_mibf* m, uint64_t* out3);
+int btlbf_mibf_id_counts(btlbf_mibf* m, uint64_t* counts, uint64_t n_ids, uint64_t* saturated);
+int btlbf_mibf_download(btlbf_mibf* m, void* host_dst);
+int btlbf_mibf_upload(btlbf_mibf* m, const void* host_src);
+int btlbf_mibf_download_counts(btlbf_mibf* m, void* host_dst);
+int btlbf_mibf_store(btlbf_mibf* m, const char* path);
+int btlbf_mibf_load(btlbf_mibf** out, const char* path, btlbf_filter* f, unsigned id_bytes);
+
 /* ---- multi-GPU hash-range sharding ------------------------------------------------
  * The M-bit filter is cut into n_shards contiguous bit ranges; shard g (btlbf_create_shard) holds
  * positions [g*M/n, (g+1)*M/n).  Routing is by POSITION, so the concatenated shard bodies are the
