@@ -1,6 +1,386 @@
-// csrc/host_internal.hpp -- host-side helpers shared by the C-ABI translation units.
+// csrc/host_internal.hpp -- what the host units of the C ABI share, and only that: error plumbing, the filter object and
+// its lazy-clear protocol, the staging pool and the mailbox, parameter blocks, sequence views, and the entry of the
+// sequence path into the partitioned pipeline.  Defined in: capi.cpp (errors, clear protocol, dev_pool, mailbox,
+// parameter blocks, make_filter, views), host_seq.cpp (seq_precheck), host_partition.cpp (the pipeline; its planner's
+// types are private to it), host_aux.cpp (rank_build).  fastx.cpp uses btlbf_set_error alone.
 #pragma once
 #include "../../include/btlbf.h"
+#include "internal.hpp"
+
+#include <map>
+#include <mutex>
+#include <string>
+#include <vector>
 
 // set the thread-local message behind btlbf_last_error() and return `code` (capi.cpp)
 int btlbf_set_error(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+
+// -------------------------------------------------------------------------------------------------
+// filter object
+// -------------------------------------------------------------------------------------------------
+struct btlbf_filter {
+	// every entry point that takes the filter holds this for its whole duration: a filter keeps device
+	// scratch, event lists and a scalar buffer between calls, so concurrent callers are serialised here
+	// (recursive: btlbf_store -> btlbf_store_shard, btlbf_apply_routed -> btlbf_apply_routed_bins)
+	mutable std::recursive_mutex mu;
+	int kind = BTLBF_BLOOM;
+	int device = 0;
+	uint64_t size = 0;        // global bits / counters
+	uint64_t size_bytes = 0;  // global bytes
+	uint64_t local_bytes = 0; // bytes held here
+	uint64_t alloc_bytes = 0; // local_bytes rounded up to 16 (zero padded)
+	unsigned h = 0, k = 0, thr = 0;
+	double dfpr = 0.0;
+	uint64_t n_entry = 0, t_entry = 0;
+	unsigned bits_per_counter = 8;
+	unsigned shard_index = 0, shard_count = 1;
+	void* d_data = nullptr;
+	// btlbf_clear is LAZY: it only sets this.  The next partitioned insert builds every segment from zero in LDS
+	// and writes it (no memset of the array, no read sweep for that batch); any other entry point that touches
+	// the array zeroes it first (materialize_clear)
+	bool lazy_zero = false;
+	// the clear is ordered on the caller's stream: clear_ev is recorded there, and whichever stream carries the
+	// zeroing out (materialize_clear, or the fresh partitioned insert) waits for it first, so work that was queued
+	// before the clear on the caller's stream cannot run after (or beside) the zeroing
+	hipEvent_t clear_ev = nullptr;
+	bool clear_ev_pending = false;
+	// ... and the zeroing itself, once some stream carries it out, is an event too: a call on ANOTHER stream (another
+	// host thread's BTLBF_STREAM_PER_THREAD, say) that finds lazy_zero already false must not look at the array
+	// while that memset is still in flight -- it waits for zero_ev first (materialize_clear)
+	hipEvent_t zero_ev = nullptr;
+	hipStream_t zero_stream = nullptr;
+	bool zero_ev_pending = false;
+	// set once btlbf_device_ptr has handed the raw pointer out: the caller may keep it, so from then on a clear
+	// zeroes eagerly on its stream (a lazily cleared array would show stale contents through that pointer)
+	bool ptr_exposed = false;
+	btlbf::ModParams mod{};
+	btlbf::HashParams hp{};
+	// spaced seeds
+	uint64_t* d_pos_tab = nullptr;
+	uint16_t* d_dc_idx = nullptr;
+	std::vector<std::string> seed_strs; // as given to btlbf_set_spaced_seeds (a miBF made from this filter stores them)
+	// small device scratch for counters
+	unsigned long long* d_scalar = nullptr; // 4 x u64
+	// partitioned insert (partition_kernels.hip): mode + cached scratch
+	int insert_mode = BTLBF_INSERT_AUTO;
+	int query_mode = BTLBF_INSERT_AUTO;
+	void* d_part = nullptr;
+	uint64_t part_bytes = 0;
+	void* d_split = nullptr; // split query: compacted reads + their bitmaps, cached like d_part
+	uint64_t split_bytes = 0;
+	void* d_flags = nullptr; // split query: cold flags of the reads + their prefix sums (small)
+	uint64_t flags_bytes = 0;
+	uint64_t part_budget = 0; // 0 = derive from free HBM
+	// optional per-kernel timing with HIP events on the launch stream (btlbf_set_profiling)
+	bool profiling = false;
+	struct Span {
+		int slot;
+		hipEvent_t e0, e1;
+	};
+	std::vector<Span> spans;
+	double prof_ms[BTLBF_PROF_SLOTS] = {0};
+	unsigned prof_calls[BTLBF_PROF_SLOTS] = {0};
+};
+
+namespace btlbf {
+
+// Every error return of the host units passes here BEFORE the locals of the failing call are destroyed: it sets the
+// message, drains the device (capi.cpp says why) and returns `code`
+int fail(int code, const char* fmt, ...);
+
+#define HIP_TRY(expr)                                                                              \
+	do {                                                                                           \
+		hipError_t e__ = (expr);                                                                   \
+		if (e__ != hipSuccess)                                                                     \
+			return fail(BTLBF_EHIP, "%s failed: %s", #expr, hipGetErrorString(e__));               \
+	} while (0)
+
+struct FilterLock {
+	const btlbf_filter* f;
+	explicit FilterLock(const btlbf_filter* f_)
+	  : f(f_)
+	{
+		if (f)
+			f->mu.lock();
+	}
+	~FilterLock()
+	{
+		if (f)
+			f->mu.unlock();
+	}
+	// give the filter back early: a read-only call that has launched its kernel (on the caller's own stream, with
+	// the caller's own buffers) only waits from here on, and other threads' calls may as well run meanwhile
+	void release()
+	{
+		if (f)
+			f->mu.unlock();
+		f = nullptr;
+	}
+	FilterLock(const FilterLock&) = delete;
+	FilterLock& operator=(const FilterLock&) = delete;
+};
+
+// the lazy clear (capi.cpp): stream s is about to carry out a pending clear / a pending clear takes effect now on s
+hipError_t order_after_clear(btlbf_filter* f, hipStream_t s);
+hipError_t materialize_clear(btlbf_filter* f, hipStream_t s);
+
+// every launch of a kernel that reads or writes the array directly goes through this check: an entry point that
+// forgot MATERIALIZE would otherwise read uninitialised HBM (the fresh partitioned insert is the one legitimate
+// user of a lazily cleared array and does not come this way)
+#define REQUIRE_MATERIALIZED(f)                                                                               \
+	do {                                                                                                      \
+		if ((f)->lazy_zero)                                                                                   \
+			return fail(BTLBF_EINVAL, "internal error: %s line %d launches on a lazily cleared array", __func__, \
+			            __LINE__);                                                                            \
+	} while (0)
+#define MATERIALIZE(f, s)                                                                              \
+	do {                                                                                               \
+		hipError_t em__ = materialize_clear(const_cast<btlbf_filter*>(f), static_cast<hipStream_t>(s)); \
+		if (em__ != hipSuccess)                                                                        \
+			return fail(BTLBF_EHIP, "clearing the filter failed: %s", hipGetErrorString(em__));         \
+	} while (0)
+
+// times one kernel launch with a pair of events when profiling is on
+struct ProfSpan {
+	btlbf_filter* f;
+	hipStream_t s;
+	int idx = -1;
+	ProfSpan(btlbf_filter* f_, int slot, hipStream_t s_)
+	  : f(f_)
+	  , s(s_)
+	{
+		if (!f->profiling)
+			return;
+		btlbf_filter::Span sp{slot, nullptr, nullptr};
+		if (hipEventCreate(&sp.e0) != hipSuccess || hipEventCreate(&sp.e1) != hipSuccess)
+			return;
+		(void)hipEventRecord(sp.e0, s);
+		f->spans.push_back(sp);
+		idx = (int)f->spans.size() - 1;
+	}
+	~ProfSpan()
+	{
+		if (idx >= 0)
+			(void)hipEventRecord(f->spans[idx].e1, s);
+	}
+};
+
+struct DeviceGuard {
+	int prev = -1;
+	bool ok = true;
+	explicit DeviceGuard(int dev)
+	{
+		if (hipGetDevice(&prev) != hipSuccess) {
+			ok = false;
+			return;
+		}
+		if (prev != dev && hipSetDevice(dev) != hipSuccess)
+			ok = false;
+	}
+	~DeviceGuard()
+	{
+		if (prev >= 0)
+			(void)hipSetDevice(prev);
+	}
+};
+
+// Small device buffers of HOST-mode calls (staged sequences, result buffers, hash rows) come from a pool:
+// hipMalloc + hipFree per call cost more than the kernels of a per-read or per-k-mer call (the drop-in shims'
+// ntHashIterator, contains(kmer), insertAndCheck make one such call each).  Power-of-two size classes up to
+// 64 MiB, per device, at most 512 MiB parked.  A pooled buffer goes back only when the call that used it has
+// synchronised its stream (every HOST-mode entry point does before it returns), so no work is pending on it.
+struct DevPool {
+	static constexpr size_t kMaxClass = 64u << 20, kMaxParked = 512u << 20;
+	std::mutex mu;
+	std::map<std::pair<int, size_t>, std::vector<void*>> parked;
+	size_t parked_bytes = 0;
+	static size_t size_class(size_t n)
+	{
+		size_t c = 4096;
+		while (c < n)
+			c <<= 1;
+		return c;
+	}
+	void* take(int dev, size_t cls)
+	{
+		std::lock_guard<std::mutex> g(mu);
+		auto it = parked.find({dev, cls});
+		if (it == parked.end() || it->second.empty())
+			return nullptr;
+		void* p = it->second.back();
+		it->second.pop_back();
+		parked_bytes -= cls;
+		return p;
+	}
+	bool give(int dev, size_t cls, void* p)
+	{
+		std::lock_guard<std::mutex> g(mu);
+		if (parked_bytes + cls > kMaxParked)
+			return false;
+		parked[{dev, cls}].push_back(p);
+		parked_bytes += cls;
+		return true;
+	}
+	// hand everything parked for `dev` (or for every device: dev < 0) back to the runtime: called when a hipMalloc
+	// fails -- a filter that nearly fills the HBM must not lose its scratch to parked staging buffers -- and by
+	// btlbf_release_scratch.  The caller has the device selected.
+	void drain(int dev)
+	{
+		std::vector<void*> out;
+		{
+			std::lock_guard<std::mutex> g(mu);
+			for (auto& kv : parked) {
+				if (dev >= 0 && kv.first.first != dev)
+					continue;
+				parked_bytes -= kv.first.second * kv.second.size();
+				out.insert(out.end(), kv.second.begin(), kv.second.end());
+				kv.second.clear();
+			}
+		}
+		for (void* p : out)
+			(void)hipFree(p);
+	}
+};
+DevPool& dev_pool(); // the one pool of the process (capi.cpp)
+
+struct DevBuf {
+	void* p = nullptr;
+	size_t pooled_class = 0;
+	int pooled_dev = -1;
+	~DevBuf()
+	{
+		if (!p)
+			return;
+		if (pooled_class && dev_pool().give(pooled_dev, pooled_class, p))
+			return;
+		(void)hipFree(p);
+	}
+	hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 16); }
+	// for buffers whose user synchronises its stream before this object dies (HOST-mode staging)
+	hipError_t alloc_pooled(size_t n)
+	{
+		if (n > DevPool::kMaxClass || hipGetDevice(&pooled_dev) != hipSuccess)
+			return alloc(n);
+		const size_t cls = DevPool::size_class(n ? n : 16);
+		if ((p = dev_pool().take(pooled_dev, cls)) != nullptr) {
+			pooled_class = cls;
+			return hipSuccess;
+		}
+		hipError_t e = hipMalloc(&p, cls);
+		if (e != hipSuccess) { // out of memory with buffers parked: give them back and try once more
+			(void)hipGetLastError();
+			dev_pool().drain(pooled_dev);
+			e = hipMalloc(&p, cls);
+		}
+		if (e == hipSuccess)
+			pooled_class = cls;
+		return e;
+	}
+	template <class T>
+	T* as()
+	{
+		return static_cast<T*>(p);
+	}
+};
+
+// A pinned, GPU-mapped mailbox per host thread for small HOST-mode calls: the kernel reads its input from and
+// writes its results to it directly (zero copy), so such a call is one launch and one stream synchronisation
+// instead of staging buffers and three or four copies.  Freed when its thread ends.
+struct Mailbox {
+	static constexpr size_t kBytes = 1u << 20;
+	uint8_t* host = nullptr;
+	uint8_t* dev = nullptr;
+	// a thread that ends gives its pinned megabytes back (a process that starts a thread per task would otherwise pin
+	// memory without bound) -- unless the HIP runtime is already shutting down: hipHostFree then fails, harmlessly
+	~Mailbox()
+	{
+		if (host)
+			(void)hipHostFree(host);
+		host = dev = nullptr;
+	}
+	bool get()
+	{
+		if (host)
+			return true;
+		void* h = nullptr;
+		if (hipHostMalloc(&h, kBytes, hipHostMallocMapped | hipHostMallocPortable) != hipSuccess) {
+			(void)hipGetLastError();
+			return false;
+		}
+		void* d = nullptr;
+		if (hipHostGetDevicePointer(&d, h, 0) != hipSuccess) {
+			(void)hipGetLastError();
+			(void)hipHostFree(h);
+			return false;
+		}
+		host = static_cast<uint8_t*>(h);
+		dev = static_cast<uint8_t*>(d);
+		return true;
+	}
+};
+Mailbox& mailbox(); // the calling thread's mailbox for the current device (capi.cpp)
+
+// parameter blocks and the filter object (capi.cpp)
+void fill_hash_params(HashParams& hp, unsigned k, unsigned h);
+int build_spaced(HashParams& hp, const char* const* seeds, unsigned n_seeds, unsigned h2,
+                 uint64_t** d_pos, uint16_t** d_dc);
+void fill_mod(ModParams& m, uint64_t size, uint64_t lo, uint64_t len);
+int make_filter(btlbf_filter** out, int kind, uint64_t size, uint64_t size_bytes, unsigned shard_index,
+                unsigned shard_count, unsigned h, unsigned k, unsigned thr, int device);
+
+// device-resident view of a caller's sequence buffer (+ layout), staging host memory if needed
+struct SeqView {
+	DevBuf seq_buf, starts_buf;
+	const uint8_t* d_seq = nullptr;
+	LayoutParams lay{nullptr, 0, 0};
+};
+
+int check_layout(const btlbf_layout* l, uint64_t len);
+int make_view(SeqView& v, const char* seq, uint64_t len, const btlbf_layout* l, int mem, hipStream_t s);
+SeqArgs base_args(const btlbf_filter* f, const SeqView& v, uint64_t len);
+int seq_precheck(const btlbf_filter* f, uint64_t len); // host_seq.cpp
+inline uint64_t bitmap_bytes(uint64_t len) { return (len + 63) / 64 * 8; }
+
+// copy a device bitmap / array back to the caller when the call was BTLBF_HOST
+struct OutBuf {
+	DevBuf dev;
+	void* host = nullptr;
+	size_t n = 0;
+	void* d = nullptr;
+	int prepare(void* user, size_t nbytes, int mem, bool zero, hipStream_t s)
+	{
+		n = nbytes;
+		if (!user)
+			return BTLBF_OK;
+		if (mem == BTLBF_DEVICE) {
+			d = user;
+		} else {
+			host = user;
+			HIP_TRY(dev.alloc_pooled(nbytes));
+			d = dev.p;
+		}
+		if (zero && nbytes)
+			HIP_TRY(hipMemsetAsync(d, 0, nbytes, s));
+		return BTLBF_OK;
+	}
+	int finish(hipStream_t s)
+	{
+		if (host && n)
+			HIP_TRY(hipMemcpyAsync(host, d, n, hipMemcpyDeviceToHost, s));
+		return BTLBF_OK;
+	}
+};
+
+// the sequence path enters the partitioned pipeline through these (host_partition.cpp)
+bool want_partitioned(const btlbf_filter* f, uint64_t len, int counting_op = -1);
+int partitioned_insert(btlbf_filter* f, const SeqArgs& base, hipStream_t s, bool* done);
+int partitioned_contains(btlbf_filter* f, const SeqArgs& base, uint8_t* hit_bits, uint8_t* valid_bits,
+                         uint64_t* counts, hipStream_t s, bool* done, bool defer_hit_count = false);
+int want_partitioned_query(btlbf_filter* f, const SeqArgs& base, hipStream_t s, bool* yes);
+int split_contains(btlbf_filter* f, const SeqArgs& a, int direct_op, hipStream_t s, int* decided);
+
+// The rank structure of a whole bit filter (host_aux.cpp): *d_il gets n_blocks records of 9 uint64_t, which the caller
+// owns, and *ones the popcount.  After an allocation that failed *d_il is null; after a build that failed it is not.
+hipError_t rank_build(const btlbf_filter* f, uint64_t** d_il, uint64_t* n_blocks, uint64_t* ones);
+
+} // namespace btlbf

@@ -1,0 +1,662 @@
+// csrc/host_mibf.cpp -- the multi-index Bloom filter (miBF stages 2-4): the ID array over the rank structure of a bit
+// filter: create, insert IDs, saturate, query, statistics, files (kernels: mibf_kernels.hip; the rank structure itself
+// is built by rank_build, host_aux.cpp).
+#include "../../include/btlbf.h"
+#include "internal.hpp"
+#include "host_internal.hpp"
+
+#include <algorithm>
+#include <cerrno>
+#include <cstdio>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+using namespace btlbf;
+
+// -------------------------------------------------------------------------------------------------
+// multi-index Bloom filter (miBF stages 2-4): the ID array over the rank structure (mibf_kernels.hip)
+// -------------------------------------------------------------------------------------------------
+struct btlbf_mibf {
+	std::mutex mu;
+	int device = 0;
+	unsigned id_bytes = 2, h = 0, k = 0;
+	uint64_t n_bits = 0, n_blocks = 0, pop = 0;
+	uint64_t budget = 0; // 0 = kMibfDefaultScratch
+	ModParams mod{};
+	HashParams hp{};
+	std::vector<std::string> seeds;
+	uint64_t* d_il = nullptr;
+	void* d_data = nullptr;   // pop T, padded to 4 bytes (the saturation OR is a 32-bit atomic)
+	void* d_counts = nullptr; // pop T
+	uint64_t* d_pos_tab = nullptr;
+	uint16_t* d_dc_idx = nullptr;
+	unsigned long long* d_stat = nullptr; // 4 x u64
+};
+
+namespace {
+
+constexpr uint64_t kMibfDefaultScratch = 2ull << 30;
+constexpr uint32_t kMibfMaxHashHost = 8;
+
+void mibf_free(btlbf_mibf* m)
+{
+	if (!m)
+		return;
+	(void)hipFree(m->d_il);
+	(void)hipFree(m->d_data);
+	(void)hipFree(m->d_counts);
+	(void)hipFree(m->d_pos_tab);
+	(void)hipFree(m->d_dc_idx);
+	(void)hipFree(m->d_stat);
+	delete m;
+}
+
+uint64_t mibf_array_bytes(const btlbf_mibf* m) { return (m->pop * m->id_bytes + 3) / 4 * 4 + 4; }
+
+// MIBloomFilter(hashNum, k, bv, seeds) + getEmptyMIBF (MIBloomFilter.hpp:122-147, MIBFConstructSupport.hpp:92-99).
+// want_pop != ~0: the popcount the ID array must have (a file's size field; EFORMAT otherwise)
+int mibf_make(btlbf_mibf** out, btlbf_filter* f, unsigned id_bytes, const std::vector<std::string>& seeds,
+              uint64_t want_pop)
+{
+	if (f->kind != BTLBF_BLOOM || f->shard_count != 1)
+		return fail(BTLBF_EINVAL, "miBF: needs a whole bit filter");
+	if (f->h == 0 || f->h > kMibfMaxHashHost)
+		return fail(BTLBF_EINVAL, "miBF: %u hash values per window (1..%u supported)", f->h, kMibfMaxHashHost);
+	HashParams hp;
+	fill_hash_params(hp, f->k, f->h);
+	btlbf_mibf* m = new btlbf_mibf();
+	m->device = f->device;
+	m->id_bytes = id_bytes;
+	m->h = f->h;
+	m->k = f->k;
+	m->seeds = seeds;
+	DeviceGuard g(f->device);
+	if (!seeds.empty()) {
+		std::vector<const char*> sp;
+		for (const auto& x : seeds)
+			sp.push_back(x.c_str());
+		int rc = build_spaced(hp, sp.data(), (unsigned)sp.size(), 1, &m->d_pos_tab, &m->d_dc_idx);
+		if (rc) {
+			mibf_free(m);
+			return rc;
+		}
+		if (!part_supported(hp)) {
+			mibf_free(m);
+			return fail(BTLBF_EINVAL, "miBF: these spaced seeds leave out more than %u distinct positions", kMaxDcu);
+		}
+	}
+	m->hp = hp;
+	m->n_bits = f->size;
+	fill_mod(m->mod, f->size, 0, f->size);
+	hipError_t e = hipMalloc((void**)&m->d_stat, 64);
+	if (e == hipSuccess)
+		e = rank_build(f, &m->d_il, &m->n_blocks, &m->pop);
+	if (e != hipSuccess && !m->d_il) {
+		(void)hipGetLastError();
+		mibf_free(m);
+		return fail(BTLBF_ENOMEM, "miBF: rank structure of %llu bits", (unsigned long long)f->size);
+	}
+	if (e != hipSuccess) {
+		mibf_free(m);
+		return fail(BTLBF_EHIP, "miBF: %s", hipGetErrorString(e));
+	}
+	if (want_pop != ~0ull && m->pop != want_pop) {
+		const unsigned long long got = m->pop;
+		mibf_free(m);
+		return fail(BTLBF_EFORMAT, "miBF: the bit vector has %llu set bits, the file %llu IDs", got,
+		            (unsigned long long)want_pop);
+	}
+	e = hipMalloc(&m->d_data, mibf_array_bytes(m));
+	if (e == hipSuccess)
+		e = hipMalloc(&m->d_counts, mibf_array_bytes(m));
+	if (e == hipSuccess)
+		e = hipMemset(m->d_data, 0, mibf_array_bytes(m));
+	if (e == hipSuccess)
+		e = hipMemset(m->d_counts, 0, mibf_array_bytes(m));
+	if (e == hipSuccess)
+		e = hipDeviceSynchronize();
+	if (e != hipSuccess) {
+		(void)hipGetLastError();
+		mibf_free(m);
+		return fail(BTLBF_ENOMEM, "miBF: ID array of %llu entries", (unsigned long long)m->pop);
+	}
+	*out = m;
+	return BTLBF_OK;
+}
+
+// the sequences of one call: device buffer, a host copy of the sequence boundaries (batches are cut on them), ids
+struct MibfCall {
+	SeqView v;
+	DevBuf ids_buf;
+	const uint32_t* d_ids = nullptr;
+	uint64_t n_seqs = 0;
+	uint32_t L = 0;
+	std::vector<uint64_t> starts; // ragged layouts: n_seqs + 1 offsets
+	uint64_t start(uint64_t s) const { return L ? s * L : starts[s]; }
+};
+
+int mibf_prepare(MibfCall& c, const char* seq, uint64_t len, const btlbf_layout* layout, const uint32_t* ids, int mem,
+                 hipStream_t s)
+{
+	if (!layout || (!layout->starts && !layout->read_len))
+		return fail(BTLBF_EINVAL, "miBF: a layout (read_len or starts) gives every sequence its id");
+	if (!ids)
+		return fail(BTLBF_EINVAL, "miBF: null ids");
+	int rc = make_view(c.v, seq, len, layout, mem, s);
+	if (rc)
+		return rc;
+	if (layout->starts) {
+		c.n_seqs = layout->n_seqs;
+		c.starts.resize(c.n_seqs + 1);
+		if (mem == BTLBF_DEVICE)
+			HIP_TRY(hipMemcpy(c.starts.data(), layout->starts, (c.n_seqs + 1) * 8, hipMemcpyDeviceToHost));
+		else
+			memcpy(c.starts.data(), layout->starts, (c.n_seqs + 1) * 8);
+		if (c.starts[0] != 0 || c.starts[c.n_seqs] != len)
+			return fail(BTLBF_EINVAL, "starts[0] must be 0 and starts[n_seqs] must equal len");
+		for (uint64_t i = 0; i < c.n_seqs; ++i)
+			if (c.starts[i + 1] < c.starts[i])
+				return fail(BTLBF_EINVAL, "starts must not decrease");
+	} else {
+		c.L = layout->read_len;
+		c.n_seqs = len / c.L;
+	}
+	if (mem == BTLBF_DEVICE) {
+		c.d_ids = ids;
+	} else {
+		HIP_TRY(c.ids_buf.alloc((c.n_seqs + 1) * 4));
+		if (c.n_seqs)
+			HIP_TRY(hipMemcpyAsync(c.ids_buf.p, ids, c.n_seqs * 4, hipMemcpyHostToDevice, s));
+		c.d_ids = c.ids_buf.as<uint32_t>();
+	}
+	return BTLBF_OK;
+}
+
+// sequences [s0, s1) as a buffer of their own: the layout's starts rebased to the batch's first byte
+int mibf_batch_layout(const MibfCall& c, uint64_t s0, uint64_t s1, DevBuf& starts_buf, LayoutParams& lay, hipStream_t s)
+{
+	lay.starts = nullptr;
+	lay.n_seqs = s1 - s0;
+	lay.read_len = c.L;
+	if (c.L)
+		return BTLBF_OK;
+	std::vector<uint64_t> rb(s1 - s0 + 1);
+	for (uint64_t i = s0; i <= s1; ++i)
+		rb[i - s0] = c.starts[i] - c.starts[s0];
+	HIP_TRY(starts_buf.alloc(rb.size() * 8));
+	HIP_TRY(hipMemcpyAsync(starts_buf.p, rb.data(), rb.size() * 8, hipMemcpyHostToDevice, s));
+	HIP_TRY(hipStreamSynchronize(s)); // rb is freed on return
+	lay.starts = starts_buf.as<uint64_t>();
+	return BTLBF_OK;
+}
+
+// the last sequence of the batch that starts at s0 and holds at most max_bytes bytes (at least one sequence)
+uint64_t mibf_batch_end(const MibfCall& c, uint64_t s0, uint64_t max_bytes, bool* too_big)
+{
+	uint64_t s1 = s0 + 1;
+	*too_big = c.start(s1) - c.start(s0) > max_bytes;
+	if (c.L) {
+		const uint64_t n = std::max<uint64_t>(1, max_bytes / c.L);
+		return std::min(c.n_seqs, s0 + n);
+	}
+	while (s1 < c.n_seqs && c.starts[s1 + 1] - c.starts[s0] <= max_bytes)
+		++s1;
+	return s1;
+}
+
+MibfArgs mibf_args(const btlbf_mibf* m, const uint8_t* seq, uint64_t len, const LayoutParams& lay)
+{
+	MibfArgs a;
+	memset(&a, 0, sizeof a);
+	a.seq = seq;
+	a.len = len;
+	a.layout = lay;
+	a.mod = m->mod;
+	a.hp = m->hp;
+	a.hp.dc_idx = m->d_dc_idx;
+	a.il = m->d_il;
+	a.data = m->d_data;
+	a.counts_t = m->d_counts;
+	return a;
+}
+
+unsigned bit_len(uint64_t x)
+{
+	unsigned b = 0;
+	while (x) {
+		++b;
+		x >>= 1;
+	}
+	return b;
+}
+
+#pragma pack(push, 1)
+struct MibfFileHeader { // MIBloomFilter.hpp:106-117
+	char magic[8];
+	uint32_t hlen;
+	uint64_t size;
+	uint32_t nhash;
+	uint32_t kmer;
+	uint32_t version;
+};
+#pragma pack(pop)
+static_assert(sizeof(MibfFileHeader) == 32, "packed miBF header");
+constexpr uint32_t kMibfVersion = 1;
+
+} // namespace
+
+extern "C" int btlbf_mibf_create(btlbf_mibf** out, btlbf_filter* f, unsigned id_bytes)
+{
+	if (!out || !f)
+		return fail(BTLBF_EINVAL, "null argument");
+	*out = nullptr;
+	if (id_bytes != 2 && id_bytes != 4)
+		return fail(BTLBF_EINVAL, "miBF: id_bytes must be 2 or 4 (uint16_t / uint32_t IDs), not %u", id_bytes);
+	FilterLock lk__(f);
+	if (f->hp.n_seeds && f->hp.h2 != 1)
+		return fail(BTLBF_EINVAL, "miBF: spaced seeds need h2 = 1 (MIBFQuerySupport.hpp:167-168), not %u", f->hp.h2);
+	if (btlbf_device_count() <= f->device)
+		return fail(BTLBF_EHIP, "no GPU %d: this library has no CPU path", f->device);
+	DeviceGuard g(f->device);
+	MATERIALIZE(f, nullptr);
+	HIP_TRY(hipDeviceSynchronize());
+	return mibf_make(out, f, id_bytes, f->hp.n_seeds ? f->seed_strs : std::vector<std::string>(), ~0ull);
+}
+
+extern "C" void btlbf_mibf_destroy(btlbf_mibf* m)
+{
+	if (!m)
+		return;
+	DeviceGuard g(m->device);
+	mibf_free(m);
+}
+
+extern "C" uint64_t btlbf_mibf_size(const btlbf_mibf* m) { return m ? m->pop : 0; }
+extern "C" uint64_t btlbf_mibf_bits(const btlbf_mibf* m) { return m ? m->n_bits : 0; }
+extern "C" unsigned btlbf_mibf_hash_num(const btlbf_mibf* m) { return m ? m->h : 0; }
+extern "C" unsigned btlbf_mibf_kmer_size(const btlbf_mibf* m) { return m ? m->k : 0; }
+
+extern "C" int btlbf_mibf_set_scratch(btlbf_mibf* m, uint64_t bytes)
+{
+	if (!m)
+		return fail(BTLBF_EINVAL, "null argument");
+	std::lock_guard<std::mutex> lk(m->mu);
+	m->budget = bytes;
+	return BTLBF_OK;
+}
+
+extern "C" int btlbf_mibf_insert_ids_seqs(btlbf_mibf* m, const char* seq, uint64_t len, const btlbf_layout* layout,
+                                          const uint32_t* ids, int mem, void* stream)
+{
+	if (!m)
+		return fail(BTLBF_EINVAL, "null argument");
+	std::lock_guard<std::mutex> lk(m->mu);
+	DeviceGuard g(m->device);
+	hipStream_t s = static_cast<hipStream_t>(stream);
+	MibfCall c;
+	int rc = mibf_prepare(c, seq, len, layout, ids, mem, s);
+	if (rc)
+		return rc;
+	if (len == 0 || c.n_seqs == 0)
+		return BTLBF_OK;
+	// one batch: 4 x 8 bytes per hash value (keys, values, and the sort's output) + the sort's scratch
+	const uint64_t budget = m->budget ? m->budget : kMibfDefaultScratch;
+	const uint64_t max_bytes = std::max<uint64_t>(1, budget / (40ull * m->h));
+	uint64_t cap_bytes = 0;
+	for (uint64_t s0 = 0; s0 < c.n_seqs;) {
+		bool big;
+		const uint64_t s1 = mibf_batch_end(c, s0, max_bytes, &big);
+		if (big)
+			return fail(BTLBF_ENOMEM, "miBF: sequence %llu does not fit the scratch budget (btlbf_mibf_set_scratch)",
+			            (unsigned long long)s0);
+		cap_bytes = std::max(cap_bytes, c.start(s1) - c.start(s0));
+		s0 = s1;
+	}
+	const uint64_t cap = cap_bytes * m->h;
+	size_t temp_bytes = 0;
+	HIP_TRY(mibf_sort_temp_bytes(cap, &temp_bytes));
+	DevBuf kin, vin, kout, vout, temp;
+	if (kin.alloc(cap * 8) || vin.alloc(cap * 8) || kout.alloc(cap * 8) || vout.alloc(cap * 8) || temp.alloc(temp_bytes)) {
+		(void)hipGetLastError();
+		return fail(BTLBF_ENOMEM, "miBF: %llu bytes of insert scratch", (unsigned long long)(cap * 32 + temp_bytes));
+	}
+	for (uint64_t s0 = 0; s0 < c.n_seqs;) {
+		bool big;
+		const uint64_t s1 = mibf_batch_end(c, s0, max_bytes, &big);
+		const uint64_t b0 = c.start(s0), blen = c.start(s1) - b0, n = blen * m->h;
+		DevBuf sb;
+		LayoutParams lay;
+		if ((rc = mibf_batch_layout(c, s0, s1, sb, lay, s)))
+			return rc;
+		MibfArgs a = mibf_args(m, c.v.d_seq + b0, blen, lay);
+		a.seq_bits = std::max(1u, bit_len(s1 - s0 - 1));
+		const unsigned end_bit = bit_len(m->pop) + a.seq_bits;
+		if (end_bit > 64)
+			return fail(BTLBF_EINVAL, "miBF: %llu sequences in one batch of a %llu-entry ID array",
+			            (unsigned long long)(s1 - s0), (unsigned long long)m->pop);
+		a.keys = kin.as<uint64_t>();
+		a.vals = vin.as<uint64_t>();
+		HIP_TRY(launch_mibf_seq(0 /* MIBF_EMIT */, m->id_bytes, a, s));
+		HIP_TRY(mibf_sort_pairs(temp.p, temp_bytes, kin.as<uint64_t>(), kout.as<uint64_t>(), vin.as<uint64_t>(),
+		                        vout.as<uint64_t>(), n, end_bit, s));
+		HIP_TRY(launch_mibf_insert_apply(m->id_bytes, kout.as<uint64_t>(), vout.as<uint64_t>(), n, a.seq_bits, c.d_ids, s0,
+		                                 m->d_data, m->d_counts, s));
+		s0 = s1;
+	}
+	HIP_TRY(hipStreamSynchronize(s)); // scratch is freed on return
+	return BTLBF_OK;
+}
+
+extern "C" int btlbf_mibf_saturate_seqs(btlbf_mibf* m, const char* seq, uint64_t len, const btlbf_layout* layout,
+                                        const uint32_t* ids, int order, uint64_t* counts4, int mem, void* stream)
+{
+	if (!m)
+		return fail(BTLBF_EINVAL, "null argument");
+	if (order != BTLBF_ORDER_PARALLEL && order != BTLBF_ORDER_SERIAL)
+		return fail(BTLBF_EINVAL, "order must be BTLBF_ORDER_PARALLEL or BTLBF_ORDER_SERIAL");
+	std::lock_guard<std::mutex> lk(m->mu);
+	DeviceGuard g(m->device);
+	hipStream_t s = static_cast<hipStream_t>(stream);
+	MibfCall c;
+	int rc = mibf_prepare(c, seq, len, layout, ids, mem, s);
+	if (rc)
+		return rc;
+	const uint64_t budget = m->budget ? m->budget : kMibfDefaultScratch;
+	HIP_TRY(hipMemsetAsync(m->d_stat, 0, 32, s));
+	if (order == BTLBF_ORDER_SERIAL) {
+		// hash rows of a batch (8 bytes per hash value + the window bitmap), then one lane in buffer order
+		const uint64_t max_bytes = std::max<uint64_t>(1, budget / (8ull * m->h + 1));
+		DevBuf rows, valid;
+		bool alloc = false;
+		for (uint64_t s0 = 0; s0 < c.n_seqs;) {
+			bool big;
+			const uint64_t s1 = mibf_batch_end(c, s0, max_bytes, &big);
+			if (big)
+				return fail(BTLBF_ENOMEM, "miBF: sequence %llu does not fit the scratch budget", (unsigned long long)s0);
+			const uint64_t b0 = c.start(s0), blen = c.start(s1) - b0;
+			if (!alloc) {
+				const uint64_t cap = std::min<uint64_t>(len, max_bytes) + 64;
+				if (rows.alloc(cap * 8 * m->h) || valid.alloc(bitmap_bytes(cap))) {
+					(void)hipGetLastError();
+					return fail(BTLBF_ENOMEM, "miBF: serial saturation scratch");
+				}
+				alloc = true;
+			}
+			DevBuf sb;
+			LayoutParams lay;
+			if ((rc = mibf_batch_layout(c, s0, s1, sb, lay, s)))
+				return rc;
+			SeqArgs h;
+			memset(&h, 0, sizeof h);
+			h.seq = c.v.d_seq + b0;
+			h.len = blen;
+			h.layout = lay;
+			h.hp = m->hp;
+			h.hp.dc_idx = m->d_dc_idx;
+			fill_mod(h.mod, 8, 0, 8);
+			h.hashes = rows.as<uint64_t>();
+			h.valid_bits = valid.as<uint8_t>();
+			HIP_TRY(launch_seq_op(OP_HASH_ONLY, h, s));
+			HIP_TRY(launch_mibf_serial_saturate(m->id_bytes, rows.as<uint64_t>(), valid.as<uint64_t>(), blen, m->h, m->mod,
+			                                    m->d_il, lay, c.d_ids, s0, m->d_data, m->d_counts, m->d_stat, s));
+			s0 = s1;
+		}
+	} else if (len) {
+		// decisions against the snapshot: mutations (rank, window) 16 bytes + 16 more for their sort, saturated ranks 8
+		// bytes each; half of the budget each
+		const uint64_t cap_mut = budget / 2 / 40, cap_sat = budget / 2 / 8;
+		DevBuf kin, vin, sat, cnt;
+		if (kin.alloc(cap_mut * 8) || vin.alloc(cap_mut * 8) || sat.alloc(cap_sat * 8) || cnt.alloc(16)) {
+			(void)hipGetLastError();
+			return fail(BTLBF_ENOMEM, "miBF: %llu bytes of saturation scratch", (unsigned long long)budget);
+		}
+		HIP_TRY(hipMemsetAsync(cnt.p, 0, 16, s));
+		MibfArgs a = mibf_args(m, c.v.d_seq, len, c.v.lay);
+		a.ids = c.d_ids;
+		a.keys = kin.as<uint64_t>();
+		a.vals = vin.as<uint64_t>();
+		a.sat = sat.as<uint64_t>();
+		a.cap_mut = cap_mut;
+		a.cap_sat = cap_sat;
+		a.n_out = cnt.as<unsigned long long>();
+		a.stat = m->d_stat;
+		HIP_TRY(launch_mibf_seq(1 /* MIBF_DECIDE */, m->id_bytes, a, s));
+		unsigned long long n_out[2];
+		HIP_TRY(hipMemcpyAsync(n_out, cnt.p, 16, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		if (n_out[0] > cap_mut || n_out[1] > cap_sat)
+			return fail(BTLBF_ENOMEM, "miBF: %llu mutations / %llu saturated positions exceed the scratch budget of "
+			            "%llu bytes (btlbf_mibf_set_scratch); nothing was changed",
+			            n_out[0], n_out[1], (unsigned long long)budget);
+		size_t temp_bytes = 0;
+		HIP_TRY(mibf_sort_temp_bytes(n_out[0], &temp_bytes));
+		DevBuf kout, vout, temp;
+		if (kout.alloc(n_out[0] * 8) || vout.alloc(n_out[0] * 8) || temp.alloc(temp_bytes)) {
+			(void)hipGetLastError();
+			return fail(BTLBF_ENOMEM, "miBF: saturation scratch");
+		}
+		HIP_TRY(mibf_sort_pairs(temp.p, temp_bytes, kin.as<uint64_t>(), kout.as<uint64_t>(), vin.as<uint64_t>(),
+		                        vout.as<uint64_t>(), n_out[0], bit_len(m->pop), s));
+		HIP_TRY(launch_mibf_mutate_apply(m->id_bytes, kout.as<uint64_t>(), vout.as<uint64_t>(), n_out[0], c.v.lay,
+		                                 c.d_ids, m->d_data, m->d_counts, s));
+		HIP_TRY(launch_mibf_saturate(m->id_bytes, sat.as<uint64_t>(), n_out[1], m->d_data, s));
+	}
+	uint64_t st[4];
+	HIP_TRY(hipMemcpyAsync(st, m->d_stat, 32, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	if (counts4) {
+		if (mem == BTLBF_DEVICE)
+			HIP_TRY(hipMemcpy(counts4, st, 32, hipMemcpyHostToDevice));
+		else
+			memcpy(counts4, st, 32);
+	}
+	return BTLBF_OK;
+}
+
+extern "C" int btlbf_mibf_query_seqs(btlbf_mibf* m, const char* seq, uint64_t len, const btlbf_layout* layout,
+                                     unsigned max_miss, void* values, uint64_t* match_bits, uint64_t* valid_bits,
+                                     uint64_t* counts2, int mem, void* stream)
+{
+	if (!m || !values)
+		return fail(BTLBF_EINVAL, "null argument");
+	std::lock_guard<std::mutex> lk(m->mu);
+	DeviceGuard g(m->device);
+	hipStream_t s = static_cast<hipStream_t>(stream);
+	SeqView v;
+	int rc = make_view(v, seq, len, layout, mem, s);
+	if (rc)
+		return rc;
+	OutBuf o_val, o_hit, o_valid, o_cnt;
+	if ((rc = o_val.prepare(values, len * m->h * m->id_bytes, mem, false, s)) ||
+	    (rc = o_hit.prepare(match_bits, bitmap_bytes(len), mem, false, s)) ||
+	    (rc = o_valid.prepare(valid_bits, bitmap_bytes(len), mem, false, s)) ||
+	    (rc = o_cnt.prepare(counts2, 16, mem, false, s)))
+		return rc;
+	HIP_TRY(hipMemsetAsync(m->d_stat, 0, 32, s));
+	MibfArgs a = mibf_args(m, v.d_seq, len, v.lay);
+	a.max_miss = max_miss;
+	a.values = o_val.d;
+	a.hit_bits = static_cast<uint8_t*>(o_hit.d);
+	a.valid_bits = static_cast<uint8_t*>(o_valid.d);
+	a.stat = m->d_stat;
+	HIP_TRY(launch_mibf_seq(2 /* MIBF_QUERY */, m->id_bytes, a, s));
+	if (o_cnt.d)
+		HIP_TRY(hipMemcpyAsync(o_cnt.d, m->d_stat, 16, hipMemcpyDeviceToDevice, s));
+	if ((rc = o_val.finish(s)) || (rc = o_hit.finish(s)) || (rc = o_valid.finish(s)) || (rc = o_cnt.finish(s)))
+		return rc;
+	HIP_TRY(hipStreamSynchronize(s)); // d_stat is reused by the next call
+	return BTLBF_OK;
+}
+
+extern "C" int btlbf_mibf_stats(btlbf_mibf* m, uint64_t* out3)
+{
+	if (!m || !out3)
+		return fail(BTLBF_EINVAL, "null argument");
+	std::lock_guard<std::mutex> lk(m->mu);
+	DeviceGuard g(m->device);
+	HIP_TRY(hipMemset(m->d_stat, 0, 16));
+	HIP_TRY(launch_mibf_stats(m->id_bytes, m->d_data, m->pop, m->d_stat, nullptr));
+	uint64_t st[2];
+	HIP_TRY(hipMemcpy(st, m->d_stat, 16, hipMemcpyDeviceToHost));
+	out3[0] = m->pop;
+	out3[1] = st[0];
+	out3[2] = st[1];
+	return BTLBF_OK;
+}
+
+extern "C" int btlbf_mibf_id_counts(btlbf_mibf* m, uint64_t* counts, uint64_t n_ids, uint64_t* saturated)
+{
+	if (!m || (n_ids && !counts))
+		return fail(BTLBF_EINVAL, "null argument");
+	uint64_t st[3];
+	int rc = btlbf_mibf_stats(m, st);
+	if (rc)
+		return rc;
+	if (saturated)
+		*saturated = st[2];
+	if (!n_ids)
+		return BTLBF_OK;
+	std::lock_guard<std::mutex> lk(m->mu);
+	DeviceGuard g(m->device);
+	DevBuf bins;
+	HIP_TRY(bins.alloc(n_ids * 8));
+	HIP_TRY(hipMemset(bins.p, 0, n_ids * 8));
+	HIP_TRY(launch_mibf_hist(m->id_bytes, m->d_data, m->pop, n_ids, bins.as<unsigned long long>(), nullptr));
+	std::vector<uint64_t> h(n_ids);
+	HIP_TRY(hipMemcpy(h.data(), bins.p, n_ids * 8, hipMemcpyDeviceToHost));
+	for (uint64_t i = 0; i < n_ids; ++i)
+		counts[i] += h[i];
+	return BTLBF_OK;
+}
+
+extern "C" int btlbf_mibf_download(btlbf_mibf* m, void* host_dst)
+{
+	if (!m || (m->pop && !host_dst))
+		return fail(BTLBF_EINVAL, "null argument");
+	std::lock_guard<std::mutex> lk(m->mu);
+	DeviceGuard g(m->device);
+	HIP_TRY(hipMemcpy(host_dst, m->d_data, m->pop * m->id_bytes, hipMemcpyDeviceToHost));
+	return BTLBF_OK;
+}
+
+extern "C" int btlbf_mibf_upload(btlbf_mibf* m, const void* host_src)
+{
+	if (!m || (m->pop && !host_src))
+		return fail(BTLBF_EINVAL, "null argument");
+	std::lock_guard<std::mutex> lk(m->mu);
+	DeviceGuard g(m->device);
+	HIP_TRY(hipMemcpy(m->d_data, host_src, m->pop * m->id_bytes, hipMemcpyHostToDevice));
+	return BTLBF_OK;
+}
+
+extern "C" int btlbf_mibf_download_counts(btlbf_mibf* m, void* host_dst)
+{
+	if (!m || (m->pop && !host_dst))
+		return fail(BTLBF_EINVAL, "null argument");
+	std::lock_guard<std::mutex> lk(m->mu);
+	DeviceGuard g(m->device);
+	HIP_TRY(hipMemcpy(host_dst, m->d_counts, m->pop * m->id_bytes, hipMemcpyDeviceToHost));
+	return BTLBF_OK;
+}
+
+extern "C" int btlbf_mibf_store(btlbf_mibf* m, const char* path)
+{
+	if (!m || !path)
+		return fail(BTLBF_EINVAL, "null argument");
+	std::vector<uint8_t> body(m->pop * m->id_bytes);
+	int rc = btlbf_mibf_download(m, body.data());
+	if (rc)
+		return rc;
+	MibfFileHeader hd;
+	memcpy(hd.magic, "MIBLOOMF", 8);
+	hd.hlen = (uint32_t)(sizeof hd + m->k * m->seeds.size());
+	hd.size = m->pop;
+	hd.nhash = m->h;
+	hd.kmer = m->k;
+	hd.version = kMibfVersion;
+	FILE* fp = fopen(path, "wb");
+	if (!fp)
+		return fail(BTLBF_EIO, "error: `%s': %s", path, strerror(errno));
+	bool ok = fwrite(&hd, sizeof hd, 1, fp) == 1;
+	for (const auto& sd : m->seeds)
+		ok = ok && fwrite(sd.data(), 1, m->k, fp) == m->k;
+	ok = ok && (body.empty() || fwrite(body.data(), 1, body.size(), fp) == body.size());
+	ok = (fclose(fp) == 0) && ok;
+	if (!ok)
+		return fail(BTLBF_EIO, "error: `%s': write failed", path);
+	return BTLBF_OK;
+}
+
+extern "C" int btlbf_mibf_load(btlbf_mibf** out, const char* path, btlbf_filter* f, unsigned id_bytes)
+{
+	if (!out || !path || !f)
+		return fail(BTLBF_EINVAL, "null argument");
+	*out = nullptr;
+	if (id_bytes != 2 && id_bytes != 4)
+		return fail(BTLBF_EINVAL, "miBF: id_bytes must be 2 or 4 (uint16_t / uint32_t IDs), not %u", id_bytes);
+	// the checks of MIBloomFilter(path) (MIBloomFilter.hpp:149-248), all before the GPU is touched
+	FILE* fp = fopen(path, "rb");
+	if (!fp)
+		return fail(BTLBF_EIO, "file \"%s\" could not be read: %s", path, strerror(errno));
+	MibfFileHeader hd;
+	std::vector<std::string> seeds;
+	std::vector<uint8_t> body;
+	int rc = BTLBF_OK;
+	if (fread(&hd, sizeof hd, 1, fp) != 1) {
+		rc = fail(BTLBF_EFORMAT, "%s: Failed to Load header", path);
+	} else if (memcmp(hd.magic, "MIBLOOMF", 8) != 0) {
+		rc = fail(BTLBF_EFORMAT, "%s: Bloom Filter type does not match", path);
+	} else {
+		if (hd.hlen > sizeof hd) {
+			for (unsigned i = 0; i < hd.nhash && !rc; ++i) {
+				std::string sd(hd.kmer, '\0');
+				if (hd.kmer > 4096 || fread(&sd[0], 1, hd.kmer, fp) != hd.kmer)
+					rc = fail(BTLBF_EFORMAT, "%s: Failed to load spaced seed string", path);
+				seeds.push_back(sd);
+			}
+		}
+		if (!rc && hd.hlen != sizeof hd + (uint64_t)hd.kmer * seeds.size())
+			rc = fail(BTLBF_EFORMAT, "%s: Multi Index Bloom Filter header length: %u does not match expected length",
+			          path, hd.hlen);
+		if (!rc && hd.version != kMibfVersion)
+			rc = fail(BTLBF_EFORMAT, "%s: Multi Index Bloom Filter version does not match: %u expected: %u", path,
+			          hd.version, kMibfVersion);
+		if (!rc) {
+			const long cur = ftell(fp);
+			fseek(fp, 0, SEEK_END);
+			const uint64_t file_size = (uint64_t)ftell(fp) - hd.hlen;
+			fseek(fp, cur, SEEK_SET);
+			if (file_size != hd.size * id_bytes)
+				rc = fail(BTLBF_EFORMAT, "%s does not match size given by its header. Size: %llu vs %llu bytes.", path,
+				          (unsigned long long)file_size, (unsigned long long)(hd.size * id_bytes));
+		}
+		if (!rc) {
+			body.resize(hd.size * id_bytes);
+			if (!body.empty() && fread(body.data(), 1, body.size(), fp) != body.size())
+				rc = fail(BTLBF_EIO, "file \"%s\" could not be read.", path);
+		}
+	}
+	fclose(fp);
+	if (rc)
+		return rc;
+	FilterLock lk__(f);
+	if (f->h != hd.nhash || f->k != hd.kmer)
+		return fail(BTLBF_EFORMAT, "miBF: the file has %u hashes of k = %u, the bit filter %u of k = %u", hd.nhash,
+		            hd.kmer, f->h, f->k);
+	if (btlbf_device_count() <= f->device)
+		return fail(BTLBF_EHIP, "no GPU %d: this library has no CPU path", f->device);
+	DeviceGuard g(f->device);
+	MATERIALIZE(f, nullptr);
+	HIP_TRY(hipDeviceSynchronize());
+	btlbf_mibf* m = nullptr;
+	if ((rc = mibf_make(&m, f, id_bytes, seeds, hd.size)))
+		return rc;
+	if (!body.empty() && hipMemcpy(m->d_data, body.data(), body.size(), hipMemcpyHostToDevice) != hipSuccess) {
+		mibf_free(m);
+		return fail(BTLBF_EHIP, "miBF: upload failed");
+	}
+	*out = m;
+	return BTLBF_OK;
+}

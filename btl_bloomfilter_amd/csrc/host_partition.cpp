@@ -1,0 +1,1277 @@
+// csrc/host_partition.cpp -- the partitioned pipeline on the host side: planning (segments, levels, caps, scratch),
+// the partitioned insert and query, the split query, and the multi-GPU routing entry points over the same planner.
+//
+// PartPlan, PartLevel, PartTail, RoutePlan, ensure_scratch, the fail-list constants and every plan_* function are
+// private to this unit; the sequence path (host_seq.cpp) enters through want_partitioned, partitioned_insert,
+// partitioned_contains, want_partitioned_query and split_contains (host_internal.hpp).  Kernels:
+// partition_kernels.hip, part_hash_inst.hip.
+#include "../../include/btlbf.h"
+#include "internal.hpp"
+#include "host_internal.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+using namespace btlbf;
+
+namespace {
+
+// partitioned query: room for the failed positions of one batch and their hash set
+static constexpr uint64_t kFailCap = 4ull << 20;          // entries
+static constexpr uint64_t kFailTableSlots = 2 * kFailCap; // power of two
+static constexpr uint64_t kFailBytes = 256 + kFailCap * 8 + kFailTableSlots * 8;
+// entries a FRESH insert batch (partitioned_insert) may report as explicit positions instead of staging them
+static constexpr uint64_t kFreshSpillCap = 16ull << 20;
+
+// The tail of the partition scratch: a query's fail list + failed-position table, or a fresh insert's spill list.
+// Inserts (fresh or not) and queries reserve the same tail, so that alternating between them never changes the
+// scratch size (a re-allocation of ~100 GB costs seconds); a caller-imposed budget below 2 GiB gets short lists
+// (more than a list holds and the batch is redone the plain way, which is always correct).
+struct PartTail {
+	uint64_t fail_cap, table_slots, spill_cap, bytes;
+};
+static PartTail part_tail(uint64_t budget)
+{
+	PartTail t;
+	const bool full = budget >= (2ull << 30);
+	t.fail_cap = full ? kFailCap : 256ull << 10;
+	t.spill_cap = full ? kFreshSpillCap : 512ull << 10;
+	t.table_slots = 2 * t.fail_cap;
+	t.bytes = std::max<uint64_t>(256 + t.fail_cap * 8 + t.table_slots * 8, 256 + t.spill_cap * 8);
+	return t;
+}
+
+// one partition level: bins of 2^shift positions, written as regions of `cap` chunks
+struct PartLevel {
+	uint32_t bins = 0;    // bins at this level (covering the local array)
+	uint32_t P = 0;       // bins per writer block (pass A: all of them; split: the fan-out)
+	uint32_t regions = 0; // writers per bin
+	uint32_t cap = 0;     // chunks per region
+	uint32_t shift = 0;   // log2(positions per bin)
+	uint32_t wseg = 0;    // level 0 only: bins of `wseg` segments each instead (plan_level0); `shift` is then unused
+	uint32_t alloc_bins = 0; // bins the arrays hold at a time (== bins unless the level is processed in groups)
+	uint64_t cnt_bytes = 0, ent_bytes = 0;
+	uint32_t* cnt = nullptr;
+	uint32_t* ent = nullptr;
+	PartOut out() const { return PartOut{P, regions, cap, cnt, ent}; }
+	PartIn in() const { return PartIn{1, alloc_bins, regions, cap, cnt, ent}; }
+};
+
+struct PartPlan {
+	uint32_t seg_shift = 19;
+	uint64_t n_seg = 0;
+	uint32_t group_bins = 0; // level-0 bins split + applied together (one-split plans); 0 = all at once
+	int n_levels = 0; // lv[0] = pass A output (or the exchanged data), lv[1..] = split outputs
+	PartLevel lv[3];
+	uint64_t tiles_per_batch = 0;
+	uint64_t bytes_total = 0;
+	// pass A's overlapped schedule keeps the entries that find their ring full in a late image per workgroup and
+	// round parity (part_hash_inst.hip): [regions][2][late_cap] words behind the tail of the scratch
+	uint32_t* late_buf = nullptr;
+	uint32_t late_cap = 0;
+};
+
+// chunks a region needs for `mean_entries` expected entries (Poisson: mean + 8 sigma) plus the
+// partially filled chunk flushed at kernel end
+uint32_t chunks_for(double mean_entries, uint32_t tail_chunks)
+{
+	const double m = mean_entries + 8.0 * std::sqrt(mean_entries + 1.0) + 32.0;
+	return (uint32_t)std::min<double>(4.0e9, std::ceil(m / (double)kChunk)) + tail_chunks;
+}
+
+unsigned ceil_log2(uint64_t x)
+{
+	unsigned b = 0;
+	while ((1ull << b) < x)
+		++b;
+	return b;
+}
+
+// mloc = positions held locally; unit_shift = log2(positions per byte): 3 for bits, 0 for uint8_t counters
+bool plan_segments(uint64_t mloc, PartPlan& pl, uint32_t unit_shift = 3)
+{
+	// 64 KiB segments (two pass-C workgroups per CU) as long as they number at most 2^19, else 128 KiB:
+	// with more than 512 x 1024 segments pass A would need 1024 level-0 bins, whose 32-entry rings make
+	// a quarter of the entries take the late path (measured: pass A 63 -> 54 ms at 512 bins; the
+	// read-only pass C loses 0.7 ms per launch with one workgroup per CU)
+	const uint32_t small = 16 + unit_shift;
+	pl.seg_shift = small;
+	if (((mloc + (1ull << small) - 1) >> small) > 512ull * 1024)
+		pl.seg_shift = small + 1;
+	pl.n_seg = (mloc + (1ull << pl.seg_shift) - 1) >> pl.seg_shift;
+	// up to 2^20 segments: pass A x one split pass; up to 2^22 (a 256 GiB bit array and beyond): two split passes
+	// (entries stay 32-bit: 1024 level-0 bins of at most 2^32 positions)
+	return pl.n_seg <= 4096ull * 1024;
+}
+
+// Slices of a split pass: workgroup (bin, slice) of bins_g input bins, each slice taking every `slices`-th input
+// region of its bin (at most r_in).  About two workgroups per CU, but a whole number of rounds over the CUs: with
+// 48 bins per group (a 3 x 2^37-bit filter) the old rule, ceil(512 / bins), gave 528 workgroups -- two full rounds of
+// 256 and a third for 16 of them, and the split pass took 5.8 ms instead of 4.2.  Looked for between half of that rule's
+// count and 16 (pass C walks up to 16 regions per segment one by one, kApplyFewRegions) or the rule's count if larger.
+uint32_t split_slices(uint32_t bins_g, uint32_t r_in, uint32_t cus)
+{
+	const uint32_t want = std::max(1u, std::min(r_in, (2 * cus + bins_g - 1) / bins_g)); // the old rule
+	const uint32_t hi = std::max(1u, std::min(r_in, std::max(want, 16u)));
+	uint32_t best = want;
+	double best_cost = 1e30;
+	for (uint32_t s = std::max(1u, want / 2); s <= hi; ++s) {
+		const uint64_t wg = (uint64_t)bins_g * s;
+		const double rounds = (double)((wg + cus - 1) / cus);
+		// time ~ rounds x work per workgroup; a slight preference for the grid the rule aimed at
+		const double cost = rounds / (double)wg * (1.0 + 0.02 * std::abs((double)s - (double)want) / (double)want);
+		if (cost < best_cost) {
+			best_cost = cost;
+			best = s;
+		}
+	}
+	return best;
+}
+
+// append the split levels that take bins of 2^lv[0].shift positions down to segments
+bool plan_splits(PartPlan& pl, uint32_t regions_in_total, uint32_t cus = 256)
+{
+	pl.n_levels = 1;
+	uint32_t regions_in = regions_in_total;
+	if (pl.lv[0].wseg) { // bins of wseg segments: one split pass, wseg ways, straight to (real) segment numbers
+		PartLevel& o = pl.lv[1];
+		o.P = pl.lv[0].wseg;
+		o.bins = pl.lv[0].bins * o.P;
+		o.shift = pl.seg_shift;
+		o.regions = split_slices(pl.lv[0].bins, regions_in, cus);
+		pl.n_levels = 2;
+	} else {
+		const uint32_t rb = pl.lv[0].shift - pl.seg_shift;
+		if (rb == 0)
+			return true;
+		if (rb > 20)
+			return false;
+		const uint32_t fan[2] = {rb <= 10 ? rb : rb - rb / 2, rb <= 10 ? 0 : rb / 2};
+		for (int j = 0; j < 2 && fan[j]; ++j) {
+			PartLevel& in = pl.lv[pl.n_levels - 1];
+			PartLevel& o = pl.lv[pl.n_levels];
+			o.P = 1u << fan[j];
+			o.bins = in.bins * o.P;
+			o.shift = in.shift - fan[j];
+			o.regions = split_slices(in.bins, regions_in, cus);
+			regions_in = o.regions;
+			++pl.n_levels;
+		}
+	}
+	// the split levels and the apply pass run in groups of level-0 bins (split a group all the way
+	// down, apply its segments, next group): the arrays of the split levels then hold one group
+	// instead of the whole batch, so a batch can be almost twice as large for the same scratch and the
+	// filter is swept fewer times
+	pl.group_bins = 0;
+	if (pl.n_levels >= 2 && pl.lv[0].bins >= 16) {
+		pl.group_bins = (pl.lv[0].bins + 7) / 8;
+		uint32_t bins_g = pl.group_bins, r_in = regions_in_total;
+		for (int j = 1; j < pl.n_levels; ++j) {
+			pl.lv[j].regions = split_slices(bins_g, r_in, cus);
+			r_in = pl.lv[j].regions;
+			bins_g *= pl.lv[j].P;
+		}
+	}
+	return true;
+}
+
+// capacities + byte sizes for `entries` expected entries in the whole batch
+void plan_caps(PartPlan& pl, double entries, int first_level)
+{
+	pl.bytes_total = 0;
+	for (int j = first_level; j < pl.n_levels; ++j) {
+		PartLevel& l = pl.lv[j];
+		// the last level has n_seg useful bins although bins may be rounded up
+		const double useful = j == pl.n_levels - 1 ? (double)std::min<uint64_t>(pl.n_seg, l.bins) : (double)l.bins;
+		l.cap = chunks_for(entries / (useful * l.regions), 1);
+		l.alloc_bins = l.bins;
+		if (j >= 1 && pl.group_bins) {
+			l.alloc_bins = pl.group_bins;
+			for (int i = 1; i <= j; ++i)
+				l.alloc_bins *= pl.lv[i].P;
+		}
+		l.cnt_bytes = ((uint64_t)l.alloc_bins * l.regions * 4 + 255) / 256 * 256;
+		l.ent_bytes = (uint64_t)l.alloc_bins * l.regions * l.cap * (kChunk * 4);
+		pl.bytes_total += l.cnt_bytes + l.ent_bytes;
+	}
+}
+
+uint8_t* carve_levels(PartPlan& pl, uint8_t* p, int first_level)
+{
+	for (int j = first_level; j < pl.n_levels; ++j) {
+		pl.lv[j].cnt = reinterpret_cast<uint32_t*>(p);
+		p += pl.lv[j].cnt_bytes;
+		pl.lv[j].ent = reinterpret_cast<uint32_t*>(p);
+		p += pl.lv[j].ent_bytes;
+	}
+	return p;
+}
+
+int ensure_scratch(btlbf_filter* f, uint64_t bytes, bool* ok)
+{
+	*ok = true;
+	if (bytes <= f->part_bytes)
+		return BTLBF_OK;
+	(void)hipFree(f->d_part);
+	f->d_part = nullptr;
+	f->part_bytes = 0;
+	hipError_t e = hipMalloc(&f->d_part, bytes);
+	if (e != hipSuccess) { // parked staging buffers of HOST-mode calls may be what is missing
+		(void)hipGetLastError();
+		dev_pool().drain(f->device);
+		e = hipMalloc(&f->d_part, bytes);
+	}
+	if (e != hipSuccess) {
+		(void)hipGetLastError();
+		f->d_part = nullptr;
+		*ok = false; // no room for scratch: the caller falls back to the direct kernels
+		return BTLBF_OK;
+	}
+	f->part_bytes = bytes;
+	return BTLBF_OK;
+}
+
+uint64_t scratch_budget(btlbf_filter* f)
+{
+	if (f->part_budget)
+		return f->part_budget;
+	size_t free_b = 0, total_b = 0;
+	if (hipMemGetInfo(&free_b, &total_b) != hipSuccess)
+		return 0;
+	return (uint64_t)((double)(free_b + f->part_bytes) * 0.80);
+}
+
+unsigned cu_count(int device)
+{
+	int cus = 256;
+	(void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+	return (unsigned)cus;
+}
+
+// pass A gives every workgroup (= region) ceil(tiles / regions) tiles: capacities are planned for the
+// fullest region, which matters when a batch has only a few tiles per workgroup
+uint64_t tiles_for_caps(uint64_t tiles, uint32_t regions)
+{
+	return regions ? (tiles + regions - 1) / regions * regions : tiles;
+}
+
+// expected probes of one full pass-A tile (+1 so that capacities never come out as zero)
+double probes_per_tile(const btlbf_filter* f, const PartTiling& tl)
+{
+	return tl.windows_per_tile * f->hp.h + 1.0;
+}
+
+// how level-0 bins map to positions, for the kernels (PartSide::bin_wseg)
+void side_bins(PartSide& sd, const PartPlan& pl)
+{
+	sd.bin_wseg = pl.lv[0].wseg;
+	sd.bin_magic = pl.lv[0].wseg ? (uint32_t)(((1ull << 32) + pl.lv[0].wseg - 1) / pl.lv[0].wseg) : 0;
+	sd.bin_seg_shift = pl.seg_shift;
+	sd.bin_width = pl.lv[0].wseg << pl.seg_shift;
+}
+
+// run the split levels lv[1..] over the level-0 data `in0`, then the apply / test pass
+// in0 holds level-0 bins [bin_offset, bin_offset + n_bins0) of the local array (bin i of in0 = absolute bin
+// bin_offset + i); the whole array by default
+int run_levels(btlbf_filter* f, PartPlan& pl, PartIn in0, const PartSide& sd, int query, hipStream_t s,
+               uint32_t bin_offset = 0, uint32_t n_bins0 = 0)
+{
+	const int exact = sd.counting && !query; // counter increments: every entry exactly once
+	if (f->lazy_zero && !(sd.fresh && !query)) // only a fresh insert may run on a lazily cleared array
+		return fail(BTLBF_EINVAL, "internal error: partition passes on a lazily cleared array");
+	const int prof_split = query ? BTLBF_PROF_QUERY_SPLIT : BTLBF_PROF_INSERT_SPLIT;
+	const int prof_apply = query ? BTLBF_PROF_QUERY_TEST : BTLBF_PROF_INSERT_APPLY;
+	if (n_bins0 == 0)
+		n_bins0 = pl.lv[0].bins - bin_offset;
+	// group by group: split the group's level-0 bins all the way down, then apply its segments
+	// (plans without groups: one group of everything)
+	const uint32_t group = pl.n_levels >= 2 && pl.group_bins ? pl.group_bins : n_bins0;
+	for (uint32_t b0 = 0; b0 < n_bins0; b0 += group) {
+		PartIn in = in0;
+		uint32_t first_in = b0, abs_first = bin_offset + b0, n_in = std::min(group, n_bins0 - b0);
+		uint32_t in_shift = pl.lv[0].shift;
+		for (int j = 1; j < pl.n_levels; ++j) {
+			ProfSpan ps(f, prof_split, s);
+			HIP_TRY(launch_part_split(f->d_data, in, first_in, abs_first, n_in, pl.lv[j].out(), pl.lv[j].shift,
+			                          in_shift, sd, query, exact, s));
+			in = pl.lv[j].in();
+			first_in = 0;
+			abs_first *= pl.lv[j].P;
+			n_in *= pl.lv[j].P;
+			in_shift = pl.lv[j].shift;
+		}
+		const uint64_t seg_first = abs_first;
+		if (seg_first >= pl.n_seg)
+			break;
+		const uint64_t n_seg = std::min<uint64_t>(n_in, pl.n_seg - seg_first);
+		ProfSpan ps(f, prof_apply, s);
+		HIP_TRY(launch_part_apply(f->d_data, f->local_bytes, pl.seg_shift, seg_first, n_seg, in, sd, query, s));
+	}
+	return BTLBF_OK;
+}
+
+// AUTO's break-even between the direct kernels and a sweep of the array, as probes per byte of the local array.
+// Measured on MI355X at 2^39 bits (tools/auto_probe.py): the direct insert costs 24.4 ms per 10^6 reads of 150 bp (21 G
+// atomics/s), the partitioned one 26.5 ms + 1.9 ms per 10^6 reads -- equal at 0.82 %; the direct query 9.3 ms per 10^6
+// reads (all hits: four gathers per k-mer), the partitioned one 17.3 ms + 1.6 per 10^6 -- equal at 1.57 %.  (Round 2's
+// rule was 2 % for both: a batch of 2x10^6 reads was inserted in 48.7 ms instead of 30.4.)
+constexpr double kAutoInsertRatio = 0.0095, kAutoQueryRatio = 0.0165;
+// plan_level0: calls of this many probes or more (4x10^9 k-mers at h = 4) take 256 level-0 bins where 512 are the rule
+constexpr double kWideSplitProbes = 1.6e10;
+
+// the segment size and the level-0 bins (pass A's output) of this filter's local array; false = no partitioned path
+// probes a call over `len` bases sends to this filter's local array (a shard keeps its window's share) -- or, with a
+// scratch budget imposed by the caller, what one batch of that budget holds (about 5.5 bytes of scratch per probe): the
+// figure plan_level0's batch-size rule goes by.  (Deterministic on purpose: the split query plans twice and both plans
+// must agree; the free-memory budget would not be the same figure twice.)
+double call_probes(const btlbf_filter* f, uint64_t len)
+{
+	const double all = (double)len * f->hp.h * ((double)f->mod.shard_len / (double)f->mod.size);
+	return f->part_budget ? std::min(all, (double)f->part_budget / 5.5) : all;
+}
+
+// `call_probes`: probes of the whole call (0 = unknown), for the one choice that depends on the batch size
+bool plan_level0(const btlbf_filter* f, PartPlan& pl, double call_probes = 0)
+{
+	if (!plan_segments(f->mod.shard_len, pl, f->kind == BTLBF_COUNTING8 ? 0 : 3))
+		return false;
+	PartLevel& l0 = pl.lv[0];
+	if (pl.n_seg <= 1024) {
+		l0.bins = (uint32_t)pl.n_seg;
+		l0.shift = pl.seg_shift;
+	} else { // split the segment index bits evenly between pass A and pass B
+		unsigned b1 = (ceil_log2(pl.n_seg) + 1) / 2; // pass B takes the larger half: pass A gains more from big rings
+		// 2^17 < segments <= 2^18 (bit filters of 8 .. 16 GiB): 512 bins and a 512-way split by that rule, or 256 bins
+		// and a 1024-way split.  Pass A is 6 % (plain ntHash: 40.2 -> 37.9 ms per 6x10^9 k-mers) to 8.5 % (four spaced
+		// seeds: 89.7 -> 82.1) faster on 128-entry rings; the 1024-way split pass costs the same per launch in batches
+		// of 6x10^9 k-mers and 0.4 ms more (of 1.8) in batches of 2.4x10^9 (tools/quick_bench.py with BTLBF_SPLIT_BITS,
+		// DESIGN.md B.2) -- so for large calls only.
+		if (ceil_log2(pl.n_seg) == 18 && call_probes >= kWideSplitProbes)
+			b1 = 10;
+		if (const char* e = getenv("BTLBF_SPLIT_BITS")) { // tuning knob: segment-index bits left to pass B
+			const int v = atoi(e);
+			if (v >= 1 && v <= 10 && ceil_log2(pl.n_seg) - v <= 10)
+				b1 = (unsigned)v;
+		}
+		if (ceil_log2(pl.n_seg) > b1 + 10)
+			b1 = ceil_log2(pl.n_seg) - 10; // pass A writes at most 1024 bins
+		l0.shift = pl.seg_shift + b1;
+		l0.bins = (uint32_t)((pl.n_seg + (1ull << b1) - 1) >> b1);
+		if (l0.shift > 32)
+			return false; // (cannot happen below 2^22 segments)
+		// A bin count that is no power of two leaves staging rings of pass A unused while the others take more
+		// entries per round than they are sized for: 3 x 2^37 bits gave 384 bins on the 512-ring geometry, a third
+		// more entries per ring and round, and pass A took 22.2 ms per 2.4x10^9 k-mers where a filter of 512 bins and the
+		// same reduction takes 18.6.  So the bins are made of a whole number of SEGMENTS instead, as many as fill the
+		// geometry's rings (768 segments per bin there, 512 bins); pass B then splits wseg ways.  One split level only.
+		const uint32_t rings = 1u << ceil_log2(l0.bins);
+		if (l0.bins < rings && b1 <= 10) {
+			l0.wseg = (uint32_t)((pl.n_seg + rings - 1) / rings);
+			l0.bins = (uint32_t)((pl.n_seg + l0.wseg - 1) / l0.wseg);
+		}
+	}
+	l0.P = l0.bins;
+	l0.alloc_bins = l0.bins;
+	return true;
+}
+
+// plan the single-GPU pipeline for a buffer and (re)allocate the scratch;
+// *ok = false means "not applicable, use the direct kernel"
+int part_prepare(btlbf_filter* f, const SeqArgs& base, PartTail* tail, PartPlan& pl, PartTiling* tiling,
+                 uint8_t** extra, bool* ok, int mode, double auto_ratio)
+{
+	*ok = false;
+	if (!plan_level0(f, pl, call_probes(f, base.len)))
+		return BTLBF_OK;
+	PartLevel& l0 = pl.lv[0];
+	l0.regions = cu_count(f->device); // pass-A workgroups: one per CU
+	if (!plan_splits(pl, l0.regions, cu_count(f->device)) || !part_hash_fits(f->hp, l0.P))
+		return BTLBF_OK;
+	*tiling = part_tiling(f->hp, l0.P, base.layout, base.len);
+	const uint64_t budget = scratch_budget(f);
+	*tail = part_tail(budget);
+	// (a caller-imposed budget below 2 GiB keeps its scratch for the entries: pass A then runs its plain schedule)
+	pl.late_cap = budget >= (2ull << 30) ? part_late_cap() : 0;
+	const uint64_t late_bytes = (uint64_t)l0.regions * 2 * pl.late_cap * sizeof(uint32_t);
+	const uint64_t extra_bytes = ((tail->bytes + 255) / 256) * 256 + late_bytes;
+	// a shard fed every rank's reads (ShardedBloomFilter's gather mode) keeps only its window's share
+	const double ppt = probes_per_tile(f, *tiling) * ((double)f->mod.shard_len / (double)f->mod.size);
+	uint64_t tiles = tiling->n_tiles;
+	for (int iter = 0; iter < 64; ++iter) {
+		plan_caps(pl, (double)tiles_for_caps(tiles, l0.regions) * ppt, 0);
+		pl.bytes_total += extra_bytes;
+		if (pl.bytes_total <= budget || tiles <= 1)
+			break;
+		const double ratio = (double)budget / (double)pl.bytes_total;
+		const uint64_t nt = (uint64_t)((double)tiles * ratio * 0.95);
+		tiles = nt >= tiles ? tiles - 1 : (nt ? nt : 1);
+	}
+	if (pl.bytes_total > budget)
+		return BTLBF_OK;
+	// AUTO: a batch that the scratch budget has cut small is not worth a sweep of the array either (the rule
+	// want_partitioned applies to the whole call, applied to one batch): a filter that nearly fills the HBM
+	// leaves a few GB for scratch, and the direct kernels are then the faster path
+	if (mode == BTLBF_INSERT_AUTO && tiles < tiling->n_tiles && (double)tiles * ppt < auto_ratio * (double)f->local_bytes)
+		return BTLBF_OK;
+	pl.tiles_per_batch = tiles;
+	int rc = ensure_scratch(f, pl.bytes_total, ok);
+	if (rc || !*ok)
+		return rc;
+	*extra = carve_levels(pl, static_cast<uint8_t*>(f->d_part), 0);
+	pl.late_buf = pl.late_cap ? reinterpret_cast<uint32_t*>(*extra + ((tail->bytes + 255) / 256) * 256) : nullptr;
+	return BTLBF_OK;
+}
+
+// hit_bits := hit_bits with the windows owning a failed position cleared, for seq tiles
+// [first, first+n) of the direct kernels' tiling
+int resolve_range(btlbf_filter* f, const SeqArgs& base, uint8_t* hit_bits, const uint64_t* fail_list, uint64_t n_fail,
+                  uint64_t* table, uint64_t max_slots, uint64_t first, uint64_t n, hipStream_t s)
+{
+	SeqArgs d = base;
+	d.first_tile = first;
+	d.n_tiles = n;
+	d.hit_bits = hit_bits;
+	d.valid_bits = nullptr;
+	d.counts = nullptr;
+	// the table is sized to the set (load <= 1/4): a few thousand failed positions make a table that stays in
+	// L2, and every probe of every window of the range is looked up in it
+	uint64_t slots = 1024;
+	while (slots < 4 * n_fail && slots < max_slots)
+		slots <<= 1;
+	HIP_TRY(hipMemsetAsync(table, 0, slots * 8, s));
+	HIP_TRY(launch_failset_build(fail_list, n_fail, table, slots - 1, s));
+	d.buckets = table;
+	d.bucket_cap = slots - 1;
+	HIP_TRY(launch_seq_op(OP_BF_RESOLVE, d, s));
+	return BTLBF_OK;
+}
+
+// ---- multi-GPU routing (SURVEY.md 8e on the partitioned pipeline) -------------------------------------
+// The GLOBAL filter (size = f->mod.size, a power of two) is cut into B = 512 (or 1024) level-0 bins; with W shards
+// owner g holds bins [g*1024/W, (g+1)*1024/W).  An origin partitions its probes into those bins (pass
+// A, regions = its CU count); the block of one owner is contiguous, so the exchange is a fixed-size
+// all-to-all of [B/W bins][regions][cap][kChunk] uint32 plus the entry counts.
+struct RoutePlan {
+	uint32_t n_windows = 1;        // position windows routed one after the other (see route_plan)
+	uint32_t shards_per_window = 1;
+	uint32_t window_shift = 0;     // log2(positions per window)
+	uint32_t bins = 1024; // level-0 bins over ONE window of the global position space
+	uint32_t shift0 = 0;  // log2(positions per level-0 bin)
+	uint32_t bins_per_shard = 0;
+	uint32_t regions = 0;
+	uint32_t cap = 0;
+	uint64_t ent_bytes_per_shard = 0, cnt_bytes_per_shard = 0;
+};
+
+// An entry is the offset of a position inside its level-0 bin and has 32 bits; pass A stages at most 1024
+// bins.  So one routing pass covers at most 2^42 positions: a larger filter (C4: 2^43 bits on 8 GPUs) is
+// routed in WINDOWS of 2^42 positions, one pass A per window over the same reads (its WINDOW variant keeps
+// the probes inside the window; the hashing is repeated, the partitioning is not).  A window is owned by
+// n_shards / n_windows consecutive shards, and only they receive blocks of that window's pass.
+int route_plan(const btlbf_filter* f, uint64_t len, const LayoutParams& lay, unsigned n_shards, RoutePlan& rp)
+{
+	const uint64_t M = f->mod.size;
+	if (!f->mod.pow2 || n_shards == 0 || (n_shards & (n_shards - 1)) || n_shards > 1024)
+		return fail(BTLBF_EINVAL, "routing needs a filter whose global size and shard count are powers of two");
+	if (!part_supported(f->hp) || !part_hash_fits(f->hp, 1024))
+		return fail(BTLBF_EINVAL, "routing does not support this hash configuration");
+	const unsigned lm = ceil_log2(M);
+	unsigned max_window = 42; // BTLBF_ROUTE_WINDOW_BITS exists for tests: small filters then exercise several windows
+	if (const char* e = getenv("BTLBF_ROUTE_WINDOW_BITS")) {
+		const int v = atoi(e);
+		if (v >= 20 && v <= 42)
+			max_window = (unsigned)v;
+	}
+	rp.window_shift = std::min(lm, max_window);
+	rp.n_windows = 1u << (lm - rp.window_shift);
+	if (rp.n_windows > n_shards)
+		return fail(BTLBF_EINVAL, "routing a 2^%u-bit filter needs at least %u shards (windows of 2^%u positions)", lm,
+		            rp.n_windows, rp.window_shift);
+	rp.shards_per_window = n_shards / rp.n_windows;
+	// 512 level-0 bins per window (64-entry LDS rings at the origin: few late entries) as long as an entry
+	// fits 32 bits, else 1024.  BTLBF_ROUTE_BINS (power of two) exists for tests: fewer bins make small
+	// filters exercise the two-split and 32-bit-entry geometries of a 1 TiB filter on 8 GPUs
+	rp.bins = rp.window_shift - 9 <= 32 && rp.shards_per_window <= 512 ? 512 : 1024;
+	if (const char* e = getenv("BTLBF_ROUTE_BINS")) {
+		const unsigned b = (unsigned)atoi(e);
+		if (b >= rp.shards_per_window && b <= 1024 && !(b & (b - 1)))
+			rp.bins = b;
+	}
+	const unsigned lw = rp.window_shift, lb = ceil_log2(rp.bins);
+	const unsigned seg_min = f->kind == BTLBF_COUNTING8 ? 16 : 19; // positions in a 64 KiB segment
+	if (lw < lb + seg_min || lw - lb > 32 || rp.bins < rp.shards_per_window)
+		return fail(BTLBF_EINVAL, "routing supports global filters of at least 2^29 bits (2^26 counters)");
+	rp.shift0 = lw - lb;
+	rp.bins_per_shard = rp.bins / rp.shards_per_window;
+	rp.regions = cu_count(f->device);
+	const PartTiling tl = part_tiling(f->hp, rp.bins, lay, len);
+	const double entries = (double)tiles_for_caps(tl.n_tiles, rp.regions) * probes_per_tile(f, tl) / rp.n_windows;
+	rp.cap = chunks_for(entries / ((double)rp.bins * rp.regions), 1);
+	rp.ent_bytes_per_shard = (uint64_t)rp.bins_per_shard * rp.regions * rp.cap * (kChunk * 4);
+	rp.cnt_bytes_per_shard = (uint64_t)rp.bins_per_shard * rp.regions * 4;
+	return BTLBF_OK;
+}
+
+// the owner's plan for blocks routed with `rp`: split levels below the level-0 bins of this shard
+int owner_plan(btlbf_filter* f, const RoutePlan& rp, const LayoutParams& lay, uint64_t plan_len, unsigned n_blocks,
+               unsigned n_shards, PartPlan& pl)
+{
+	if (!plan_segments(f->mod.shard_len, pl, f->kind == BTLBF_COUNTING8 ? 0 : 3))
+		return fail(BTLBF_EINVAL, "shard too large for the partitioned pipeline");
+	pl.lv[0].bins = rp.bins_per_shard;
+	pl.lv[0].shift = rp.shift0;
+	pl.lv[0].regions = rp.regions * n_blocks;
+	if (pl.lv[0].shift < pl.seg_shift || !plan_splits(pl, pl.lv[0].regions, cu_count(f->device)))
+		return fail(BTLBF_EINVAL, "unsupported shard geometry");
+	// every origin sends about entries/n_shards to this shard; n_blocks origins
+	const PartTiling tl = part_tiling(f->hp, rp.bins, lay, plan_len);
+	const double entries = (double)tiles_for_caps(tl.n_tiles, rp.regions) * probes_per_tile(f, tl) * n_blocks / n_shards;
+	plan_caps(pl, entries, 1);
+	return BTLBF_OK;
+}
+
+LayoutParams layout_params(const btlbf_layout* layout)
+{
+	LayoutParams lay{nullptr, 0, 0};
+	if (layout) {
+		lay.n_seqs = layout->n_seqs;
+		lay.read_len = layout->starts ? 0 : layout->read_len;
+		lay.starts = layout->starts;
+	}
+	return lay;
+}
+
+} // namespace
+
+namespace btlbf {
+
+// decide between the direct (atomicOr per probe) and the partitioned insert
+// bit filters: insert; counting filters: incrementAll only (the conservative update of `insert` needs
+// the minimum over a k-mer's h counters, which live in different segments)
+bool want_partitioned(const btlbf_filter* f, uint64_t len, int counting_op)
+{
+	if (f->insert_mode == BTLBF_INSERT_DIRECT)
+		return false;
+	if (f->kind == BTLBF_COUNTING8 ? counting_op != BTLBF_INCREMENT_ALL : f->kind != BTLBF_BLOOM)
+		return false;
+	if (!part_supported(f->hp) || len == 0)
+		return false;
+	if (f->insert_mode == BTLBF_INSERT_PARTITIONED)
+		return true;
+	// auto: one sweep of the local array (read + write) must be cheaper than the random atomics it
+	// replaces: ~ 2*bytes/5.8e12 s against probes/21e9 s (kAutoInsertRatio); and the batch must be big
+	// enough to be worth five launches
+	const double probes = (double)len * f->hp.h * ((double)f->mod.shard_len / (double)f->mod.size);
+	return probes >= kAutoInsertRatio * (double)f->local_bytes && probes >= 4.0e6;
+}
+
+int partitioned_insert(btlbf_filter* f, const SeqArgs& base, hipStream_t s, bool* done)
+{
+	*done = false;
+	// A pending btlbf_clear is carried out by the first batch itself: pass C builds every segment from zero in
+	// LDS and writes it -- no memset of the array and no read sweep for that batch.  Pass C would also wipe what
+	// the overflow paths of passes A and B write straight into the array, so a fresh batch reports those entries
+	// as explicit positions instead (as the multi-GPU routing does) and they are applied after its last pass C;
+	// more of them than the list holds (heavily skewed input) and the batch is redone the ordinary way.
+	PartPlan pl;
+	PartTiling tiling;
+	uint8_t* extra = nullptr;
+	bool ok = false;
+	PartTail tail;
+	int rc = part_prepare(f, base, &tail, pl, &tiling, &extra, &ok, f->insert_mode, kAutoInsertRatio);
+	if (rc || !ok)
+		return rc;
+	const uint64_t total_tiles = tiling.n_tiles;
+	for (uint64_t t0 = 0; t0 < total_tiles; t0 += pl.tiles_per_batch) {
+		SeqArgs a = base;
+		a.first_tile = t0;
+		a.n_tiles = std::min<uint64_t>(pl.tiles_per_batch, total_tiles - t0);
+		for (int attempt = 0; attempt < 2; ++attempt) {
+			const bool fresh = f->lazy_zero;
+			PartSide sd;
+			memset(&sd, 0, sizeof sd);
+			sd.counting = f->kind == BTLBF_COUNTING8;
+			sd.late_buf = pl.late_buf;
+			sd.late_cap = pl.late_cap;
+			side_bins(sd, pl);
+			if (fresh) {
+				HIP_TRY(order_after_clear(f, s)); // this batch IS the clear: after the point it was asked for
+				sd.fresh = 1;
+				sd.pos_base = f->mod.shard_lo;
+				sd.spill_count = reinterpret_cast<unsigned long long*>(extra);
+				sd.spill_list = reinterpret_cast<uint64_t*>(extra + 256);
+				sd.spill_cap = tail.spill_cap;
+				HIP_TRY(hipMemsetAsync(sd.spill_count, 0, 8, s));
+			}
+			{
+				ProfSpan ps(f, BTLBF_PROF_INSERT_HASH, s);
+				HIP_TRY(launch_part_hash(a, pl.lv[0].out(), pl.lv[0].shift, sd, 0, s));
+			}
+			if ((rc = run_levels(f, pl, pl.lv[0].in(), sd, 0, s)))
+				return rc;
+			if (!fresh)
+				break;
+			f->lazy_zero = false; // every segment has been written
+			unsigned long long n_spill = 0;
+			hipError_t e = hipMemcpyAsync(&n_spill, sd.spill_count, 8, hipMemcpyDeviceToHost, s);
+			if (e == hipSuccess)
+				e = hipStreamSynchronize(s);
+			if (e == hipSuccess && n_spill <= tail.spill_cap) {
+				PartSide plain;
+				memset(&plain, 0, sizeof plain);
+				plain.counting = sd.counting;
+				e = launch_spill(f->d_data, sd.spill_list, n_spill, f->mod.shard_lo, f->mod.shard_len, 0, plain, s);
+				if (e == hipSuccess)
+					break;
+			}
+			if (e != hipSuccess) { // the batch is half applied: back to a defined (empty) state
+				f->lazy_zero = true;
+				return fail(BTLBF_EHIP, "fresh partitioned insert: %s", hipGetErrorString(e));
+			}
+			HIP_TRY(hipMemsetAsync(f->d_data, 0, f->alloc_bytes, s)); // start over, the ordinary way
+		}
+	}
+	*done = true;
+	return BTLBF_OK;
+}
+
+// Partitioned contains(): positions are partitioned exactly as for insert and
+// TESTED against each segment in LDS; positions found clear go to a (small) fail list.  A batch
+// without failures is finished: every clean window hits.  Otherwise the failed positions become a
+// cache-resident hash set and one more hashing pass clears the windows that own one of them.  Too
+// many failures (a miss-heavy batch) and the batch is redone by the direct gather kernel.
+// hit_bits (device) is required; valid_bits and counts are optional.
+// base.read_mask (the split query): those reads are left out -- no bits, no counts; defer_hit_count: counts[1] is left
+// for the caller, who adds the left-out reads' answers to the bitmap first.
+int partitioned_contains(btlbf_filter* f, const SeqArgs& base, uint8_t* hit_bits, uint8_t* valid_bits,
+                         uint64_t* counts, hipStream_t s, bool* done, bool defer_hit_count)
+{
+	*done = false;
+	PartPlan pl;
+	PartTiling tiling;
+	uint8_t* extra = nullptr;
+	bool ok = false;
+	PartTail tail;
+	int rc = part_prepare(f, base, &tail, pl, &tiling, &extra, &ok, f->query_mode, kAutoQueryRatio);
+	if (rc || !ok)
+		return rc;
+	const uint64_t total_tiles = tiling.n_tiles;
+	PartSide sd;
+	memset(&sd, 0, sizeof sd);
+	sd.fail_count = reinterpret_cast<unsigned long long*>(extra);
+	sd.fail_list = reinterpret_cast<uint64_t*>(extra + 256);
+	sd.fail_cap = tail.fail_cap;
+	sd.counting = f->kind == BTLBF_COUNTING8;
+	sd.threshold = f->thr;
+	sd.late_buf = pl.late_buf;
+	sd.late_cap = pl.late_cap;
+	side_bins(sd, pl);
+	sd.pos_base = f->mod.shard_lo; // the fail set is keyed by global position
+	const int direct_op = sd.counting ? OP_CBF_QUERY : f->shard_count != 1 ? OP_BF_CONTAINS_WIN : OP_BF_CONTAINS;
+	uint64_t* table = sd.fail_list + tail.fail_cap;
+	uint64_t* ctl = reinterpret_cast<uint64_t*>(extra + 64); // two words of stream-side control next to the fail count
+	if (counts)
+		HIP_TRY(hipMemsetAsync(counts, 0, 16, s));
+	const uint64_t seq_tw = (uint64_t)seq_tile_windows();
+	const uint64_t seq_tiles_all = (base.len + seq_tw - 1) / seq_tw;
+	for (uint64_t t0 = 0; t0 < total_tiles; t0 += pl.tiles_per_batch) {
+		SeqArgs a = base;
+		a.first_tile = t0;
+		a.n_tiles = std::min<uint64_t>(pl.tiles_per_batch, total_tiles - t0);
+		a.hit_bits = hit_bits;
+		a.valid_bits = valid_bits;
+		a.counts = counts; // pass A adds the clean-window count to counts[0]
+		HIP_TRY(hipMemsetAsync(sd.fail_count, 0, 8, s));
+		{
+			ProfSpan ps(f, BTLBF_PROF_QUERY_HASH, s);
+			HIP_TRY(launch_part_hash(a, pl.lv[0].out(), pl.lv[0].shift, sd, 1, s));
+		}
+		if ((rc = run_levels(f, pl, pl.lv[0].in(), sd, 1, s)))
+			return rc;
+		// redo / refine this batch's window range with the direct kernels: their tiles that overlap the
+		// batch's bytes.  A tile more at either end is harmless: a failed position is a bit that IS clear,
+		// so clearing any window that owns it is right, and a direct redo computes the true answer.
+		// What happens is decided on the device (GATE_*): no failed position -> nothing; up to fail_cap -> they become
+		// a hash set and one hashing pass clears the windows that own one; more -> the range is redone by the direct
+		// kernel.  All launches are issued, the ones decided against return at once: no host round trip per batch.
+		const uint64_t first = t0 * tiling.tile_bytes / seq_tw;
+		const uint64_t end_b = std::min<uint64_t>(base.len, (t0 + a.n_tiles) * (uint64_t)tiling.tile_bytes);
+		const uint64_t n = std::min<uint64_t>((end_b + seq_tw - 1) / seq_tw, seq_tiles_all) - first;
+		ProfSpan ps(f, BTLBF_PROF_QUERY_RESOLVE, s);
+		HIP_TRY(launch_failset_auto(sd.fail_list, sd.fail_count, tail.fail_cap, table, tail.table_slots, ctl, s));
+		SeqArgs d = base;
+		d.first_tile = first;
+		d.n_tiles = n;
+		d.hit_bits = hit_bits;
+		d.valid_bits = nullptr;
+		d.counts = nullptr;
+		d.gate = ctl;
+		d.gate_mode = GATE_REDO;
+		REQUIRE_MATERIALIZED(f);
+		HIP_TRY(launch_seq_op(direct_op, d, s));
+		d.buckets = table;
+		d.gate_mode = GATE_RESOLVE;
+		HIP_TRY(launch_seq_op(OP_BF_RESOLVE, d, s));
+	}
+	if (counts && !defer_hit_count) // hits = set bits of the final bitmap
+		HIP_TRY(launch_popcount(hit_bits, ((base.len + 63) / 64) * 8, 0, 0,
+		                        reinterpret_cast<unsigned long long*>(counts) + 1, s));
+	*done = true;
+	return BTLBF_OK;
+}
+
+// AUTO decision for contains(): large batch, and a sample of tiles says nearly every k-mer hits
+int want_partitioned_query(btlbf_filter* f, const SeqArgs& base, hipStream_t s, bool* yes)
+{
+	*yes = false;
+	if (f->query_mode == BTLBF_INSERT_DIRECT)
+		return BTLBF_OK;
+	if (!part_supported(f->hp) || base.len == 0)
+		return BTLBF_OK;
+	if (f->query_mode == BTLBF_INSERT_PARTITIONED) {
+		*yes = true;
+		return BTLBF_OK;
+	}
+	const double live = (double)base.len * f->hp.h * ((double)f->mod.shard_len / (double)f->mod.size);
+	if (live < kAutoQueryRatio * (double)f->local_bytes || live < 4.0e6)
+		return BTLBF_OK;
+	// sample 64 tiles spread over the buffer with the direct kernel
+	const uint64_t tiles = (base.len + seq_tile_windows() - 1) / seq_tile_windows();
+	const unsigned n_s = (unsigned)std::min<uint64_t>(64, tiles);
+	HIP_TRY(hipMemsetAsync(f->d_scalar, 0, 16, s));
+	for (unsigned i = 0; i < n_s; ++i) {
+		SeqArgs a = base;
+		a.first_tile = (tiles / n_s) * i;
+		a.n_tiles = 1;
+		a.hit_bits = nullptr;
+		a.valid_bits = nullptr;
+		a.counts = reinterpret_cast<uint64_t*>(f->d_scalar);
+		a.min_out = nullptr;
+		HIP_TRY(launch_seq_op(f->kind == BTLBF_COUNTING8 ? OP_CBF_QUERY
+		                      : f->shard_count != 1      ? OP_BF_CONTAINS_WIN
+		                                                 : OP_BF_CONTAINS,
+		                      a, s));
+	}
+	unsigned long long c[2] = {0, 0};
+	HIP_TRY(hipMemcpyAsync(c, f->d_scalar, 16, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	if (c[0] == 0)
+		return BTLBF_OK;
+	// expected failed probes in the whole call (at most h per missing k-mer) must stay well below
+	// what the fail list holds per batch
+	const double miss = (double)(c[0] - c[1]) / (double)c[0];
+	*yes = miss * live < 0.25 * (double)part_tail(scratch_budget(f)).fail_cap;
+	return BTLBF_OK;
+}
+
+// contains() over fixed-length reads in AUTO mode (aux_kernels.hip, "split query"): sample every read; if the
+// misses are few enough for the fail list the whole buffer goes partitioned (*decided = 2), if hardly anything
+// hits it goes to the gather kernel (1); otherwise the reads are compacted into a warm and a cold buffer, the
+// warm one takes the partitioned path, the cold one the early-exit gather kernel, and the two bitmaps are
+// merged back into the caller's layout (3: a.hit_bits / a.valid_bits / a.counts are complete).
+int split_contains(btlbf_filter* f, const SeqArgs& a, int direct_op, hipStream_t s, int* decided)
+{
+	*decided = 0;
+	const uint32_t L = a.layout.starts ? 0 : a.layout.read_len, k = f->hp.k;
+	// whole filters only: the sampler probes f->d_data with positions of the whole array (a shard answers for its
+	// window through the WINDOW kernels; want_partitioned_query decides for it)
+	if (f->shard_count != 1 || f->mod.shard_lo != 0 || f->mod.shard_len != f->mod.size)
+		return BTLBF_OK;
+	if (f->query_mode != BTLBF_INSERT_AUTO || !L || L < k || L < 8 || f->hp.n_seeds || !part_supported(f->hp))
+		return BTLBF_OK;
+	const uint64_t n_reads = a.len / L;
+	const uint32_t W = L - k + 1;
+	const double live = (double)n_reads * W * f->hp.h;
+	if (live < kAutoQueryRatio * (double)f->local_bytes || live < 4.0e6 || n_reads >= (1ull << 32))
+		return BTLBF_OK; // small batches: the direct kernel (want_partitioned_query agrees)
+	const uint64_t n_fw = (n_reads + 63) / 64;
+	// temporaries are cached in the filter (grow-only, btlbf_release_scratch returns them): hipMalloc / hipFree
+	// of tens of GB cost more than the kernels.  The small one (flags, prefix sums) is needed by every call;
+	// the large one (compacted reads, their bitmaps) only once the split path is taken
+	auto up = [](uint64_t x) { return (x + 255) / 256 * 256; };
+	auto grow = [](void** p, uint64_t* have, uint64_t bytes) -> bool {
+		if (bytes <= *have)
+			return true;
+		(void)hipFree(*p);
+		*p = nullptr;
+		*have = 0;
+		if (hipMalloc(p, bytes) != hipSuccess) {
+			(void)hipGetLastError();
+			return false;
+		}
+		*have = bytes;
+		return true;
+	};
+	// (the flags are readable for 256 bytes behind their last word: pass A reads up to 34 words from a tile's first one on)
+	const uint64_t sz_flags = up(n_fw * 8 + 256), sz_prefix = up((n_fw + (n_fw + 1023) / 1024 + 1) * 4);
+	if (!grow(&f->d_flags, &f->flags_bytes, 256 + sz_flags + sz_prefix))
+		return BTLBF_OK; // no room: the plain paths decide (want_partitioned_query)
+	unsigned long long* d_ncold = static_cast<unsigned long long*>(f->d_flags);
+	uint64_t* d_flags = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(f->d_flags) + 256);
+	uint32_t* d_prefix = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(f->d_flags) + 256 + sz_flags);
+	unsigned long long n_cold = 0;
+	auto sample = [&](uint32_t stride, uint32_t probes2) -> int {
+		HIP_TRY(hipMemsetAsync(d_ncold, 0, 8, s));
+		{
+			ProfSpan ps(f, BTLBF_PROF_QUERY_RESOLVE, s);
+			HIP_TRY(launch_read_sample(a.seq, n_reads, L, stride, f->hp, f->mod, f->d_data, f->kind == BTLBF_COUNTING8,
+			                           f->thr, d_flags, reinterpret_cast<uint64_t*>(d_ncold), s, probes2));
+		}
+		HIP_TRY(hipMemcpyAsync(&n_cold, d_ncold, 8, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		return BTLBF_OK;
+	};
+	// what the fail list copes with / what is worth a sweep of the array, in reads
+	// (the list the partitioned path will really have: a small scratch budget gets a short one, part_tail)
+	const double few_cold = 0.25 * (double)part_tail(scratch_budget(f)).fail_cap / ((double)W * f->hp.h);
+	auto warm_too_few = [&](double n_warm_reads) {
+		const double wl = n_warm_reads * W * f->hp.h;
+		return wl < kAutoQueryRatio * (double)f->local_bytes || wl < 4.0e6;
+	};
+	// 1. an estimate from one read in 64: all-hit and all-miss buffers -- the common cases -- are recognised at
+	//    1/64 of the cost of looking at every read
+	int rc;
+	const uint32_t stride = n_reads >= (1u << 20) ? 64 : 1;
+	double cold_frac = 1.0; // estimate from the first look (unknown: assume many)
+	if (stride > 1) {
+		if ((rc = sample(stride, 0)))
+			return rc;
+		cold_frac = (double)n_cold / (double)((n_reads + stride - 1) / stride);
+		const uint64_t n_s = (n_reads + stride - 1) / stride;
+		if (n_cold == 0 && (double)n_reads * 8.0 / (double)n_s < few_cold) { // none in the sample: few overall
+			*decided = 2;
+			return BTLBF_OK;
+		}
+		if (warm_too_few((double)(n_s - n_cold) * stride * 1.5)) {
+			*decided = 1;
+			return BTLBF_OK;
+		}
+	}
+	// 2. every read.  A present read costs the sampler its probes (they all hit, so they are all loaded), and the second
+	//    sample only has to keep a foreign read from passing on ONE false-positive window: with few foreign reads, fewer
+	//    of its probes do (a read that passes all the same costs a resolve pass, never a wrong answer)
+	const uint32_t h = f->hp.h;
+	const uint32_t probes2 = cold_frac <= 0.0025 ? (h + 1) / 2 : cold_frac <= 0.025 ? std::max((h + 1) / 2, h - 1) : h;
+	if ((rc = sample(1, probes2)))
+		return rc;
+	const uint64_t n_warm = n_reads - n_cold;
+	if ((double)n_cold < few_cold) { // the fail list copes with that many misses
+		*decided = 2;
+		return BTLBF_OK;
+	}
+	if (warm_too_few((double)n_warm)) { // not worth a sweep of the array
+		*decided = 1;
+		return BTLBF_OK;
+	}
+	// ---- split ----
+	const uint64_t warm_len = n_warm * L, cold_len = n_cold * L;
+	const bool wv = a.valid_bits != nullptr;
+	// Uniform reads that pass A takes through its read grid: the warm reads stay where they are -- pass A leaves the
+	// cold ones out by their flags (zero-staged: no entries, no bits, no counts) --, only the COLD reads are gathered for
+	// the direct kernel, and their answers are ORed back into the caller's bitmaps.  The first version gathered the warm
+	// reads as well (15 GB copied and 15 GB of HBM that the partition scratch then lacked: a third batch) and merged
+	// every word of the bitmaps from two sources.
+	{
+		PartPlan pl0;
+		PartGrid g;
+		// (up to a quarter of the reads cold: beyond that the lanes pass A spends on zero-staged reads cost more than
+		// gathering the warm reads costs -- at one read in two 76 instead of 43 ms of pass A per 10^8 reads)
+		if (4 * n_cold <= n_reads && plan_level0(f, pl0, call_probes(f, a.len)) && part_read_grid(f->hp, pl0.lv[0].P, a.layout, &g)) {
+			const uint64_t szm[5] = {up(cold_len + 16), up(bitmap_bytes(cold_len) + 16), wv ? up(bitmap_bytes(cold_len) + 16) : 0,
+			                         up(n_cold * 4 + 16), a.hit_bits ? 0 : up(bitmap_bytes(a.len) + 16)};
+			uint64_t need = 0;
+			for (uint64_t v : szm)
+				need += v;
+			// (a buffer left behind by a call that gathered the warm reads as well -- 19 GB for 10^8 reads -- is given back
+			// first: the partition scratch is planned from the free HBM, and with that much less of it the pass would need
+			// a third batch, i.e. a third sweep of the array)
+			if (f->split_bytes > 4 * need + (1ull << 30)) {
+				(void)hipFree(f->d_split);
+				f->d_split = nullptr;
+				f->split_bytes = 0;
+			}
+			if (!grow(&f->d_split, &f->split_bytes, need)) {
+				*decided = 1;
+				return BTLBF_OK;
+			}
+			uint8_t* q[5];
+			{
+				uint64_t off = 0;
+				for (int i = 0; i < 5; ++i) {
+					q[i] = szm[i] ? static_cast<uint8_t*>(f->d_split) + off : nullptr;
+					off += szm[i];
+				}
+			}
+			uint8_t *cold_p = q[0], *cold_hit_p = q[1], *cold_valid_p = q[2];
+			uint32_t* cold_index = reinterpret_cast<uint32_t*>(q[3]);
+			uint8_t* hb = a.hit_bits ? a.hit_bits : q[4];
+			{
+				ProfSpan ps(f, BTLBF_PROF_QUERY_RESOLVE, s);
+				HIP_TRY(launch_flag_prefix(d_flags, n_reads, d_prefix, s));
+				HIP_TRY(launch_gather_cold_reads(a.seq, n_reads, L, d_flags, d_prefix, cold_p, cold_index, s));
+				HIP_TRY(hipMemsetAsync(cold_hit_p + bitmap_bytes(cold_len), 0, 16, s)); // (the merge reads a word further)
+				if (wv)
+					HIP_TRY(hipMemsetAsync(cold_valid_p + bitmap_bytes(cold_len), 0, 16, s));
+			}
+			SeqArgs b = a;
+			b.read_mask = reinterpret_cast<const uint32_t*>(d_flags);
+			b.hit_bits = b.valid_bits = nullptr;
+			b.counts = nullptr;
+			bool done_w = false;
+			if ((rc = partitioned_contains(f, b, hb, a.valid_bits, a.counts, s, &done_w, true)))
+				return rc;
+			if (!done_w) { // no room for the partition scratch: the gather kernel answers the whole buffer
+				*decided = 1;
+				return BTLBF_OK;
+			}
+			SeqArgs d = a;
+			d.seq = cold_p;
+			d.len = cold_len;
+			d.hit_bits = cold_hit_p;
+			d.valid_bits = cold_valid_p;
+			d.counts = a.counts; // the direct kernel ADDS its clean windows (and its hits: recounted below)
+			{
+				ProfSpan ps(f, BTLBF_PROF_QUERY_DIRECT, s);
+				REQUIRE_MATERIALIZED(f);
+				HIP_TRY(launch_seq_op(direct_op, d, s));
+			}
+			{
+				ProfSpan ps(f, BTLBF_PROF_QUERY_RESOLVE, s);
+				HIP_TRY(launch_merge_cold_bitmaps(n_cold, L, cold_index, reinterpret_cast<const uint64_t*>(cold_hit_p),
+				                                  reinterpret_cast<const uint64_t*>(cold_valid_p), reinterpret_cast<uint64_t*>(hb),
+				                                  reinterpret_cast<uint64_t*>(a.valid_bits), s));
+				if (a.counts) { // hits = set bits of the finished bitmap
+					HIP_TRY(hipMemsetAsync(a.counts + 1, 0, 8, s));
+					HIP_TRY(launch_popcount(hb, bitmap_bytes(a.len), 0, 0, reinterpret_cast<unsigned long long*>(a.counts) + 1, s));
+				}
+			}
+			*decided = 3;
+			return BTLBF_OK;
+		}
+	}
+	const uint64_t sz[6] = {up(warm_len + 16), up(cold_len + 16), up(bitmap_bytes(warm_len) + 16),
+	                        up(bitmap_bytes(cold_len) + 16), wv ? up(bitmap_bytes(warm_len) + 16) : 0,
+	                        wv ? up(bitmap_bytes(cold_len) + 16) : 0};
+	// sized for any split of a buffer this long, so that the next call's ratio does not move memory
+	const uint64_t worst = up(a.len + 32) + 512 + (wv ? 2 : 1) * (up(bitmap_bytes(a.len) + 32) + 512);
+	if (!grow(&f->d_split, &f->split_bytes, worst)) {
+		*decided = 1; // no room for the compacted copies: the gather kernel answers any mix
+		return BTLBF_OK;
+	}
+	uint8_t* bufs[6];
+	{
+		uint64_t off = 0;
+		for (int i = 0; i < 6; ++i) {
+			bufs[i] = sz[i] ? static_cast<uint8_t*>(f->d_split) + off : nullptr;
+			off += sz[i];
+		}
+		if (off > f->split_bytes)
+			return fail(BTLBF_EINVAL, "split query: buffer arithmetic");
+	}
+	uint8_t *warm_p = bufs[0], *cold_p = bufs[1], *warm_hit_p = bufs[2], *cold_hit_p = bufs[3], *warm_valid_p = bufs[4],
+	        *cold_valid_p = bufs[5];
+	{
+		ProfSpan ps(f, BTLBF_PROF_QUERY_RESOLVE, s);
+		HIP_TRY(launch_flag_prefix(d_flags, n_reads, d_prefix, s));
+		HIP_TRY(launch_compact_reads(a.seq, n_reads, L, d_flags, d_prefix, warm_p, cold_p, s));
+		// the merge reads one word past the last bit of a compacted bitmap
+		HIP_TRY(hipMemsetAsync(warm_hit_p + bitmap_bytes(warm_len), 0, 16, s));
+		HIP_TRY(hipMemsetAsync(cold_hit_p + bitmap_bytes(cold_len), 0, 16, s));
+		if (a.valid_bits) {
+			HIP_TRY(hipMemsetAsync(warm_valid_p + bitmap_bytes(warm_len), 0, 16, s));
+			HIP_TRY(hipMemsetAsync(cold_valid_p + bitmap_bytes(cold_len), 0, 16, s));
+		}
+	}
+	if (a.counts)
+		HIP_TRY(hipMemsetAsync(a.counts, 0, 16, s));
+	SeqArgs b = a;
+	b.seq = warm_p;
+	b.len = warm_len;
+	b.hit_bits = b.valid_bits = nullptr;
+	b.counts = nullptr;
+	bool done_w = false;
+	rc = partitioned_contains(f, b, warm_hit_p, warm_valid_p, a.counts, s, &done_w);
+	if (rc)
+		return rc;
+	if (!done_w) { // no room for the partition scratch: the gather kernel does the warm reads too
+		b.hit_bits = warm_hit_p;
+		b.valid_bits = warm_valid_p;
+		b.counts = a.counts;
+		ProfSpan ps(f, BTLBF_PROF_QUERY_DIRECT, s);
+		HIP_TRY(launch_seq_op(direct_op, b, s));
+	}
+	SeqArgs d = a;
+	d.seq = cold_p;
+	d.len = cold_len;
+	d.hit_bits = cold_hit_p;
+	d.valid_bits = cold_valid_p;
+	d.counts = a.counts; // the direct kernel ADDS its clean windows and hits
+	{
+		ProfSpan ps(f, BTLBF_PROF_QUERY_DIRECT, s);
+		HIP_TRY(launch_seq_op(direct_op, d, s));
+	}
+	if (a.hit_bits || a.valid_bits) {
+		ProfSpan ps(f, BTLBF_PROF_QUERY_RESOLVE, s);
+		HIP_TRY(launch_merge_split_bitmaps(a.len, L, d_flags, d_prefix, reinterpret_cast<uint64_t*>(warm_hit_p),
+		                                   reinterpret_cast<uint64_t*>(cold_hit_p), reinterpret_cast<uint64_t*>(warm_valid_p),
+		                                   reinterpret_cast<uint64_t*>(cold_valid_p), reinterpret_cast<uint64_t*>(a.hit_bits),
+		                                   reinterpret_cast<uint64_t*>(a.valid_bits), s));
+	}
+	*decided = 3;
+	return BTLBF_OK;
+}
+
+} // namespace btlbf
+
+extern "C" int btlbf_route_plan(btlbf_filter* f, uint64_t len, const btlbf_layout* layout, unsigned n_shards,
+                                uint64_t* ent_bytes_per_shard, uint64_t* cnt_bytes_per_shard)
+{
+	FilterLock lk__(f);
+	if (!f || !ent_bytes_per_shard || !cnt_bytes_per_shard)
+		return fail(BTLBF_EINVAL, "null argument");
+	LayoutParams lay{nullptr, 0, 0};
+	if (layout) {
+		lay.starts = layout->starts;
+		lay.n_seqs = layout->n_seqs;
+		lay.read_len = layout->starts ? 0 : layout->read_len;
+	}
+	RoutePlan rp;
+	int rc = route_plan(f, len, lay, n_shards, rp);
+	if (rc)
+		return rc;
+	*ent_bytes_per_shard = rp.ent_bytes_per_shard;
+	*cnt_bytes_per_shard = rp.cnt_bytes_per_shard;
+	return BTLBF_OK;
+}
+
+// planning only (no device needed): the read grid pass A would use for fixed-length reads
+extern "C" int btlbf_plan_read_grid(unsigned kmer_size, unsigned hash_num, unsigned read_len, unsigned level0_bins,
+                                    uint32_t* out4)
+{
+	if (!out4 || kmer_size == 0 || hash_num == 0 || level0_bins == 0 || level0_bins > 1024)
+		return fail(BTLBF_EINVAL, "btlbf_plan_read_grid: bad argument");
+	HashParams hp;
+	fill_hash_params(hp, kmer_size, hash_num);
+	PartGrid g;
+	(void)part_read_grid(hp, level0_bins, LayoutParams{nullptr, 0, read_len}, &g);
+	out4[0] = g.reads;
+	out4[1] = g.gpr;
+	out4[2] = g.lpad;
+	out4[3] = g.cap;
+	return BTLBF_OK;
+}
+
+extern "C" int btlbf_route_windows(btlbf_filter* f, unsigned n_shards, unsigned* n_windows,
+                                   unsigned* shards_per_window)
+{
+	FilterLock lk__(f);
+	if (!f || !n_windows || !shards_per_window)
+		return fail(BTLBF_EINVAL, "null argument");
+	RoutePlan rp;
+	int rc = route_plan(f, 1, LayoutParams{nullptr, 0, 0}, n_shards, rp);
+	if (rc)
+		return rc;
+	*n_windows = rp.n_windows;
+	*shards_per_window = rp.shards_per_window;
+	return BTLBF_OK;
+}
+
+extern "C" int btlbf_route_seqs(btlbf_filter* f, const char* seq, uint64_t len, const btlbf_layout* layout,
+                                uint64_t plan_len, unsigned n_shards, unsigned window, int query, void* send_ent,
+                                void* send_cnt, uint64_t* hit_bits, uint64_t* valid_bits, uint64_t* counts,
+                                uint64_t* spill_list, uint64_t spill_cap, uint64_t* spill_count, void* stream)
+{
+	FilterLock lk__(f);
+	int rc = seq_precheck(f, len);
+	if (rc)
+		return rc;
+	if (!send_ent || !send_cnt || !spill_list || !spill_count)
+		return fail(BTLBF_EINVAL, "null argument");
+	DeviceGuard g(f->device);
+	hipStream_t s = static_cast<hipStream_t>(stream);
+	SeqView v;
+	if ((rc = make_view(v, seq, len, layout, BTLBF_DEVICE, s)))
+		return rc;
+	RoutePlan rp;
+	if ((rc = route_plan(f, plan_len, v.lay, n_shards, rp)))
+		return rc;
+	if (window >= rp.n_windows)
+		return fail(BTLBF_EINVAL, "window %u of %u", window, rp.n_windows);
+	SeqArgs a = base_args(f, v, len);
+	// positions of the GLOBAL filter, those inside this window (all of them when there is one window)
+	fill_mod(a.mod, f->mod.size, (uint64_t)window << rp.window_shift, 1ull << rp.window_shift);
+	a.hit_bits = reinterpret_cast<uint8_t*>(hit_bits);
+	a.valid_bits = reinterpret_cast<uint8_t*>(valid_bits);
+	a.counts = counts;
+	a.first_tile = 0;
+	a.n_tiles = part_tiling(f->hp, rp.bins, v.lay, len).n_tiles;
+	PartOut out{rp.bins, rp.regions, rp.cap, static_cast<uint32_t*>(send_cnt), static_cast<uint32_t*>(send_ent)};
+	PartSide sd;
+	memset(&sd, 0, sizeof sd);
+	sd.spill_list = spill_list;
+	sd.spill_count = reinterpret_cast<unsigned long long*>(spill_count);
+	sd.spill_cap = spill_cap;
+	sd.pos_base = a.mod.shard_lo; // spilled entries travel as global positions
+	// spill_count and counts ACCUMULATE over the batches of a pass (the caller zeroes them once): no
+	// host round trip per batch, so the exchange of one batch can overlap the hashing of the next
+	if (a.n_tiles == 0) { // nothing to hash: still publish empty regions
+		HIP_TRY(hipMemsetAsync(send_cnt, 0, (size_t)rp.cnt_bytes_per_shard * rp.shards_per_window, s));
+		return BTLBF_OK;
+	}
+	ProfSpan ps(f, query ? BTLBF_PROF_QUERY_HASH : BTLBF_PROF_INSERT_HASH, s);
+	HIP_TRY(launch_part_hash(a, out, rp.shift0, sd, query, s));
+	return BTLBF_OK;
+}
+
+extern "C" int btlbf_route_geometry(btlbf_filter* f, uint64_t plan_len, const btlbf_layout* layout, unsigned n_shards,
+                                    unsigned n_blocks, uint32_t* out4)
+{
+	FilterLock lk__(f);
+	if (!f || !out4)
+		return fail(BTLBF_EINVAL, "null argument");
+	const LayoutParams lay = layout_params(layout);
+	RoutePlan rp;
+	int rc = route_plan(f, plan_len, lay, n_shards, rp);
+	if (rc)
+		return rc;
+	PartPlan pl;
+	if ((rc = owner_plan(f, rp, lay, plan_len, n_blocks ? n_blocks : n_shards, n_shards, pl)))
+		return rc;
+	out4[0] = rp.bins_per_shard;
+	out4[1] = rp.regions;
+	out4[2] = rp.cap;
+	out4[3] = pl.n_levels >= 2 && pl.group_bins ? pl.group_bins : rp.bins_per_shard;
+	return BTLBF_OK;
+}
+
+extern "C" int btlbf_owner_scratch_bytes(btlbf_filter* f, uint64_t plan_len, const btlbf_layout* layout, unsigned n_shards,
+                                         unsigned n_blocks, uint64_t* bytes)
+{
+	FilterLock lk__(f);
+	if (!f || !bytes)
+		return fail(BTLBF_EINVAL, "null argument");
+	const LayoutParams lay = layout_params(layout);
+	RoutePlan rp;
+	int rc = route_plan(f, plan_len, lay, n_shards, rp);
+	if (rc)
+		return rc;
+	PartPlan pl;
+	if ((rc = owner_plan(f, rp, lay, plan_len, n_blocks ? n_blocks : n_shards, n_shards, pl)))
+		return rc;
+	*bytes = pl.bytes_total;
+	return BTLBF_OK;
+}
+
+extern "C" int btlbf_apply_routed_bins(btlbf_filter* f, const void* recv_ent, const void* recv_cnt, unsigned n_blocks,
+                                       unsigned first_bin, unsigned n_bins, uint64_t plan_len,
+                                       const btlbf_layout* layout, unsigned n_shards, int query, uint64_t* fail_list,
+                                       uint64_t fail_cap, uint64_t* fail_count, void* stream)
+{
+	FilterLock lk__(f);
+	if (!f || !recv_ent || !recv_cnt || n_blocks == 0)
+		return fail(BTLBF_EINVAL, "null argument");
+	if (f->shard_count != n_shards)
+		return fail(BTLBF_EINVAL, "filter is shard %u of %u, not of %u", f->shard_index, f->shard_count, n_shards);
+	if (query && (!fail_list || !fail_count))
+		return fail(BTLBF_EINVAL, "query needs a fail list");
+	DeviceGuard g(f->device);
+	hipStream_t s = static_cast<hipStream_t>(stream);
+	MATERIALIZE(f, s);
+	const LayoutParams lay = layout_params(layout);
+	RoutePlan rp;
+	int rc = route_plan(f, plan_len, lay, n_shards, rp);
+	if (rc)
+		return rc;
+	PartPlan pl;
+	if ((rc = owner_plan(f, rp, lay, plan_len, n_blocks, n_shards, pl)))
+		return rc;
+	const uint32_t group = pl.n_levels >= 2 && pl.group_bins ? pl.group_bins : rp.bins_per_shard;
+	if (n_bins == 0 || first_bin + n_bins > rp.bins_per_shard || first_bin % group || (n_bins % group && first_bin + n_bins != rp.bins_per_shard))
+		return fail(BTLBF_EINVAL, "bins [%u, +%u) are not whole groups of %u of this shard's %u level-0 bins", first_bin,
+		            n_bins, group, rp.bins_per_shard);
+	bool ok = false;
+	if ((rc = ensure_scratch(f, pl.bytes_total, &ok)))
+		return rc;
+	if (!ok)
+		return fail(BTLBF_ENOMEM, "no room for %llu bytes of partition scratch", (unsigned long long)pl.bytes_total);
+	carve_levels(pl, static_cast<uint8_t*>(f->d_part), 1);
+	PartSide sd;
+	memset(&sd, 0, sizeof sd);
+	sd.pos_base = f->mod.shard_lo;
+	sd.fail_list = fail_list;
+	sd.fail_count = reinterpret_cast<unsigned long long*>(fail_count);
+	sd.fail_cap = fail_cap;
+	sd.counting = f->kind == BTLBF_COUNTING8; // incrementAll / counter >= threshold at the owner
+	sd.threshold = f->thr;
+	PartIn in0{n_blocks, n_bins, rp.regions, rp.cap, static_cast<const uint32_t*>(recv_cnt),
+	           static_cast<const uint32_t*>(recv_ent)};
+	return run_levels(f, pl, in0, sd, query, s, first_bin, n_bins);
+}
+
+extern "C" int btlbf_apply_routed(btlbf_filter* f, const void* recv_ent, const void* recv_cnt, unsigned n_blocks,
+                                  uint64_t plan_len, const btlbf_layout* layout, unsigned n_shards, int query,
+                                  uint64_t* fail_list, uint64_t fail_cap, uint64_t* fail_count, void* stream)
+{
+	FilterLock lk__(f);
+	if (!f)
+		return fail(BTLBF_EINVAL, "null argument");
+	const LayoutParams lay = layout_params(layout);
+	RoutePlan rp;
+	int rc = route_plan(f, plan_len, lay, n_shards, rp);
+	if (rc)
+		return rc;
+	return btlbf_apply_routed_bins(f, recv_ent, recv_cnt, n_blocks, 0, rp.bins_per_shard, plan_len, layout, n_shards,
+	                               query, fail_list, fail_cap, fail_count, stream);
+}
+
+extern "C" int btlbf_apply_spill(btlbf_filter* f, const uint64_t* global_pos, uint64_t n, int query,
+                                 uint64_t* fail_list, uint64_t fail_cap, uint64_t* fail_count, void* stream)
+{
+	FilterLock lk__(f);
+	if (!f || (n && !global_pos))
+		return fail(BTLBF_EINVAL, "null argument");
+	DeviceGuard g(f->device);
+	MATERIALIZE(f, stream);
+	PartSide sd;
+	memset(&sd, 0, sizeof sd);
+	sd.fail_list = fail_list;
+	sd.fail_count = reinterpret_cast<unsigned long long*>(fail_count);
+	sd.fail_cap = fail_cap;
+	sd.counting = f->kind == BTLBF_COUNTING8;
+	sd.threshold = f->thr;
+	HIP_TRY(launch_spill(f->d_data, global_pos, n, f->mod.shard_lo, f->mod.shard_len, query, sd,
+	                     static_cast<hipStream_t>(stream)));
+	return BTLBF_OK;
+}
+
+extern "C" int btlbf_resolve_seqs(btlbf_filter* f, const char* seq, uint64_t len, const btlbf_layout* layout,
+                                  const uint64_t* fail_list, uint64_t n_fail, uint64_t* hit_bits, void* stream)
+{
+	FilterLock lk__(f);
+	int rc = seq_precheck(f, len);
+	if (rc)
+		return rc;
+	if (!hit_bits || (n_fail && !fail_list))
+		return fail(BTLBF_EINVAL, "null argument");
+	if (n_fail == 0 || len == 0)
+		return BTLBF_OK;
+	if (n_fail > kFailCap)
+		return fail(BTLBF_EINVAL, "more than %llu failed positions: use the direct query", (unsigned long long)kFailCap);
+	DeviceGuard g(f->device);
+	hipStream_t s = static_cast<hipStream_t>(stream);
+	SeqView v;
+	if ((rc = make_view(v, seq, len, layout, BTLBF_DEVICE, s)))
+		return rc;
+	bool ok = false;
+	if ((rc = ensure_scratch(f, kFailTableSlots * 8, &ok)))
+		return rc;
+	if (!ok)
+		return fail(BTLBF_ENOMEM, "no room for the failed-position set");
+	SeqArgs a = base_args(f, v, len);
+	fill_mod(a.mod, f->mod.size, 0, f->mod.size); // global positions
+	return resolve_range(f, a, reinterpret_cast<uint8_t*>(hit_bits), fail_list, n_fail,
+	                     static_cast<uint64_t*>(f->d_part), kFailTableSlots, 0, 0, s);
+}

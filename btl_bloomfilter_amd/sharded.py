@@ -494,7 +494,7 @@ class ShardedBloomFilter:
         return batch, -(-longest // batch)
 
     # NOTE for the C ABI: ops.route (btlbf_route_seqs) must stay free of per-filter scratch -- it runs on a second
-    # stream while btlbf_apply_routed* uses the filter's scratch on the first (capi.cpp: route passes no late list,
+    # stream while btlbf_apply_routed* uses the filter's scratch on the first (host_partition.cpp: route passes no late list,
     # so pass A takes its plain schedule there; tests/test_sharded.py runs both streams together)
     def _routed_pass(self, reads, read_len, query, hit_bits=None, counts=None):
         """One insert / query pass over this rank's reads on the routed path.  The unit of work is a JOB =

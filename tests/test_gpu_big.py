@@ -110,7 +110,7 @@ def test_clear_is_ordered_on_the_callers_stream_and_eager_after_device_ptr(bf):
 @pytest.mark.parametrize("bits,window", [(3 << 32, False), (5 << 33, False), (7 << 34, True), (3 << 37, False), ((1 << 36) + (1 << 32), False)])
 def test_sizes_of_an_odd_multiple_of_2p32_partitioned_equals_direct(bf, bits, window):
     """hash % size (BloomFilter.hpp:190) for sizes m * 2^s, s >= 32 (3 * 2^37 bits and the like): segment counts of no
-    power of two, so pass A's bins are a whole number of segments (capi.cpp plan_level0) and positions come from the
+    power of two, so pass A's bins are a whole number of segments (host_partition.cpp plan_level0) and positions come from the
     32-bit-quotient form of the reduction -- same reads through the direct kernels and the pipeline, identical arrays
     and answers; `window`: as one shard of two, so that the WINDOW form of pass A runs too."""
     import torch
@@ -143,7 +143,7 @@ def test_sizes_of_an_odd_multiple_of_2p32_partitioned_equals_direct(bf, bits, wi
 @pytest.mark.parametrize("kind", ["plain", "spaced", "counting"])
 def test_2p18_segments_with_256_level0_bins_and_a_1024_way_split(bf, monkeypatch, kind):
     """calls of 4x10^9 k-mers and more plan a filter of 2^18 segments (2^37 bits, 2^34 counters) as 256 bins x 1024 ways
-    instead of 512 x 512 (capi.cpp plan_level0); the tests' batches are smaller than that, so the plan is forced here
+    instead of 512 x 512 (host_partition.cpp plan_level0); the tests' batches are smaller than that, so the plan is forced here
     through the tuning knob -- against the direct kernels: plain ntHash, config 5's spaced seeds, incrementAll"""
     import torch
 
@@ -342,8 +342,8 @@ def test_single_gpu_256_gib_filter_2p41_bits(bf):
     prof = f.getProfile()
     assert prof["insert_hash"][1] >= 1 and prof["insert_split"][1] >= 2
     assert f.digest() + (f.getPop(),) == direct
-    # AUTO: the call as a whole is worth a sweep of the array (probes >= 0.95 % of its bytes, capi.cpp
-    # kAutoInsertRatio), but with this little scratch one BATCH is not -> the direct kernel
+    # AUTO: the call as a whole is worth a sweep of the array (probes >= 0.95 % of its bytes,
+    # host_partition.cpp kAutoInsertRatio), but with this little scratch one BATCH is not -> the direct kernel
     del q, hit_d, hit_p
     more = bf.synth_reads_device(42, 0, 12_000_000, L)
     f.clear()

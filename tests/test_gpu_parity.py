@@ -542,7 +542,7 @@ def test_partitioned_equals_direct_odd_shapes(bf, oracle, bits, k, h):
 def test_partitioned_small_scratch_many_batches_and_skew(bf, bits):
     """a scratch cap forces several batches; 4000 copies of one read overflow their bins, which must
     fall back to direct atomics instead of dropping entries.  Sizes of no power of two: level-0 bins are then a whole
-    number of segments (capi.cpp plan_level0), and the overflow paths of passes A and B rebuild positions from them"""
+    number of segments (host_partition.cpp plan_level0), and the overflow paths of passes A and B rebuild positions from them"""
     import torch
 
     h, k, L = 4, 31, 150

@@ -52,7 +52,7 @@ def window_bits(words, n_bytes):
 @pytest.mark.parametrize("bits", [1 << 39, 3 << 37], ids=["2p39_bits", "3x2p37_bits"])
 def test_c2_bit_exact_against_the_reference(bf, ref, bits):
     """(3 * 2^37 bits: the bench line's side config of no power-of-two size -- `hash % size` by multiplication and level-0
-    bins of a whole number of segments, capi.cpp plan_level0 -- against the reference's plain `%`)"""
+    bins of a whole number of segments, host_partition.cpp plan_level0 -- against the reference's plain `%`)"""
     import torch
 
     h, k, n = 4, 31, 2_000_000

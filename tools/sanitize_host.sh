@@ -1,8 +1,8 @@
 #!/bin/bash
 # AddressSanitizer + UndefinedBehaviorSanitizer over the HOST side of the library (CPU only: GPU ASan is
-# not available on this pool): csrc/fastx.cpp (FASTA/FASTQ parser, reader threads) and csrc/capi.cpp
-# (planning, file headers, argument checks) are rebuilt instrumented and linked with the kernels as built;
-# then the CPU test cases that drive them run against that library.
+# not available on this pool): every host unit of btl_bloomfilter_amd/build.py (HOST_UNITS: the C ABI's planning, file
+# headers and argument checks, the FASTA/FASTQ parser and its reader threads) is rebuilt instrumented and linked with
+# the kernel objects as built; then the CPU test cases that drive them run against that library.
 #     tools/sanitize_host.sh            (from the repository root)
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
@@ -12,11 +12,14 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 SAN="-fsanitize=address,undefined -fno-gpu-sanitize -fno-omit-frame-pointer -g -O1"
 P=btl_bloomfilter_amd
 mkdir -p $P/_build_asan
-for u in capi fastx; do
-	$HIPCC --offload-arch=gfx950 -std=c++17 -fPIC -Wall -Wno-unused-function $SAN -c -o $P/_build_asan/$u.o $P/csrc/$u.cpp
+HOST_UNITS=$(python3 -c "from btl_bloomfilter_amd import build as b; print(' '.join(b.HOST_UNITS))")
+KERNEL_OBJS=$(python3 -c "from btl_bloomfilter_amd import build as b; print(' '.join('$P/_build/%s.o' % n for n, _, _ in b.UNITS if n not in b.HOST_UNITS))")
+HOST_OBJS=
+for u in $HOST_UNITS; do
+	(set -x; $HIPCC --offload-arch=gfx950 -std=c++17 -fPIC -Wall -Wno-unused-function $SAN -c -o $P/_build_asan/$u.o $P/csrc/$u.cpp)
+	HOST_OBJS="$HOST_OBJS $P/_build_asan/$u.o"
 done
-$HIPCC --offload-arch=gfx950 -shared -fPIC $SAN -o $P/libbtlbf_asan.so $P/_build_asan/capi.o $P/_build_asan/fastx.o \
-	$P/_build/seq_kernels.o $P/_build/aux_kernels.o $P/_build/partition_kernels.o $P/_build/part_hash_h*.o -lz
+$HIPCC --offload-arch=gfx950 -shared -fPIC $SAN -o $P/libbtlbf_asan.so $HOST_OBJS $KERNEL_OBJS -lz
 RT=$(/opt/rocm/lib/llvm/bin/clang -print-file-name=libclang_rt.asan-x86_64.so)
 [ -f "$RT" ] || RT=$(/opt/rocm/lib/llvm/bin/clang --print-file-name=libclang_rt.asan.so)
 echo "runtime: $RT"
