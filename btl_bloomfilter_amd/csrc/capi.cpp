@@ -448,9 +448,9 @@ extern "C" int btlbf_destroy(btlbf_filter* f)
 	(void)hipFree(f->d_scalar);
 	(void)hipFree(f->d_pos_tab);
 	(void)hipFree(f->d_dc_idx);
-	(void)hipFree(f->d_part);
-	(void)hipFree(f->d_split);
-	(void)hipFree(f->d_flags);
+	f->part.release();
+	f->split.release();
+	f->flags.release();
 	delete f;
 	return BTLBF_OK;
 }
@@ -471,15 +471,9 @@ extern "C" int btlbf_release_scratch(btlbf_filter* f)
 	if (!f)
 		return fail(BTLBF_EINVAL, "null filter");
 	DeviceGuard g(f->device);
-	(void)hipFree(f->d_part); // synchronises with work in flight
-	f->d_part = nullptr;
-	f->part_bytes = 0;
-	(void)hipFree(f->d_split);
-	f->d_split = nullptr;
-	f->split_bytes = 0;
-	(void)hipFree(f->d_flags);
-	f->d_flags = nullptr;
-	f->flags_bytes = 0;
+	f->part.release();
+	f->split.release();
+	f->flags.release();
 	dev_pool().drain(f->device); // parked staging buffers of HOST-mode calls (every user has synchronised)
 	return BTLBF_OK;
 }

@@ -210,7 +210,7 @@ extern "C" int btlbf_positions_seqs(btlbf_filter* f, const char* seq, uint64_t l
                                     uint64_t* valid_bits, void* stream)
 {
 	FilterLock lk__(f);
-	int rc = seq_precheck(f, len);
+	int rc = seq_precheck(f);
 	if (rc)
 		return rc;
 	if (!buckets || !bucket_counts || n_shards == 0 || n_shards > 64)

@@ -1,8 +1,9 @@
-// csrc/host_internal.hpp -- what the host units of the C ABI share, and only that: error plumbing, the filter object and
-// its lazy-clear protocol, the staging pool and the mailbox, parameter blocks, sequence views, and the entry of the
-// sequence path into the partitioned pipeline.  Defined in: capi.cpp (errors, clear protocol, dev_pool, mailbox,
-// parameter blocks, make_filter, views), host_seq.cpp (seq_precheck), host_partition.cpp (the pipeline; its planner's
-// types are private to it), host_aux.cpp (rank_build).  fastx.cpp uses btlbf_set_error alone.
+// csrc/host_internal.hpp -- what the host units of the C ABI share, and only that: error plumbing, the filter object,
+// its cached device scratch (DevScratch) and its lazy-clear protocol, the staging pool and the mailbox, parameter
+// blocks, sequence views, and the entry of the sequence path into the partitioned pipeline.  Defined in: capi.cpp
+// (errors, clear protocol, dev_pool, mailbox, parameter blocks, make_filter, views), host_seq.cpp (seq_precheck),
+// host_partition.cpp (the pipeline; its planner's types are private to it), host_aux.cpp (rank_build).  fastx.cpp uses
+// btlbf_set_error alone.
 #pragma once
 #include "../../include/btlbf.h"
 #include "internal.hpp"
@@ -15,13 +16,32 @@
 // set the thread-local message behind btlbf_last_error() and return `code` (capi.cpp)
 int btlbf_set_error(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
+namespace btlbf {
+
+// A device buffer the filter keeps between calls: hipMalloc / hipFree of tens of GB cost more than the kernels, so it
+// only ever grows, and btlbf_release_scratch and btlbf_destroy give it back.  The caller has the device selected.
+struct DevScratch {
+	void* p = nullptr;
+	uint64_t bytes = 0;
+	// room for `need` bytes (the contents are not kept); false = there is none, and the buffer is then empty
+	bool grow(uint64_t need, int device);
+	void release()
+	{
+		(void)hipFree(p); // synchronises with work in flight
+		p = nullptr;
+		bytes = 0;
+	}
+};
+
+} // namespace btlbf
+
 // -------------------------------------------------------------------------------------------------
 // filter object
 // -------------------------------------------------------------------------------------------------
 struct btlbf_filter {
 	// every entry point that takes the filter holds this for its whole duration: a filter keeps device
 	// scratch, event lists and a scalar buffer between calls, so concurrent callers are serialised here
-	// (recursive: btlbf_store -> btlbf_store_shard, btlbf_apply_routed -> btlbf_apply_routed_bins)
+	// (recursive: btlbf_store -> btlbf_store_shard)
 	mutable std::recursive_mutex mu;
 	int kind = BTLBF_BLOOM;
 	int device = 0;
@@ -64,12 +84,9 @@ struct btlbf_filter {
 	// partitioned insert (partition_kernels.hip): mode + cached scratch
 	int insert_mode = BTLBF_INSERT_AUTO;
 	int query_mode = BTLBF_INSERT_AUTO;
-	void* d_part = nullptr;
-	uint64_t part_bytes = 0;
-	void* d_split = nullptr; // split query: compacted reads + their bitmaps, cached like d_part
-	uint64_t split_bytes = 0;
-	void* d_flags = nullptr; // split query: cold flags of the reads + their prefix sums (small)
-	uint64_t flags_bytes = 0;
+	btlbf::DevScratch part;
+	btlbf::DevScratch split; // split query: compacted reads + their bitmaps
+	btlbf::DevScratch flags; // split query: cold flags of the reads + their prefix sums (small)
 	uint64_t part_budget = 0; // 0 = derive from free HBM
 	// optional per-kernel timing with HIP events on the launch stream (btlbf_set_profiling)
 	bool profiling = false;
@@ -243,6 +260,24 @@ struct DevPool {
 };
 DevPool& dev_pool(); // the one pool of the process (capi.cpp)
 
+inline bool DevScratch::grow(uint64_t need, int device)
+{
+	if (need <= bytes)
+		return true;
+	release();
+	if (hipMalloc(&p, need) != hipSuccess) { // parked staging buffers of HOST-mode calls may be what is missing
+		(void)hipGetLastError();
+		dev_pool().drain(device);
+		if (hipMalloc(&p, need) != hipSuccess) {
+			(void)hipGetLastError();
+			p = nullptr;
+			return false;
+		}
+	}
+	bytes = need;
+	return true;
+}
+
 struct DevBuf {
 	void* p = nullptr;
 	size_t pooled_class = 0;
@@ -338,7 +373,7 @@ struct SeqView {
 int check_layout(const btlbf_layout* l, uint64_t len);
 int make_view(SeqView& v, const char* seq, uint64_t len, const btlbf_layout* l, int mem, hipStream_t s);
 SeqArgs base_args(const btlbf_filter* f, const SeqView& v, uint64_t len);
-int seq_precheck(const btlbf_filter* f, uint64_t len); // host_seq.cpp
+int seq_precheck(const btlbf_filter* f); // host_seq.cpp
 inline uint64_t bitmap_bytes(uint64_t len) { return (len + 63) / 64 * 8; }
 
 // copy a device bitmap / array back to the caller when the call was BTLBF_HOST

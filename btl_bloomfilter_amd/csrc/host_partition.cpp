@@ -1,10 +1,12 @@
 // csrc/host_partition.cpp -- the partitioned pipeline on the host side: planning (segments, levels, caps, scratch),
 // the partitioned insert and query, the split query, and the multi-GPU routing entry points over the same planner.
 //
-// PartPlan, PartLevel, PartTail, RoutePlan, ensure_scratch, the fail-list constants and every plan_* function are
-// private to this unit; the sequence path (host_seq.cpp) enters through want_partitioned, partitioned_insert,
-// partitioned_contains, want_partitioned_query and split_contains (host_internal.hpp).  Kernels:
-// partition_kernels.hip, part_hash_inst.hip.
+// A call plans once and passes the plan down: part_prepare (PartPrep) for the single-GPU pipeline -- the split query
+// hands it the level-0 plan it has already made --, plan_routed (RoutePlan) for the routing entry points.  The plan
+// types, the fail-list constants, the named rules (local_probes, worth_sweep, direct_query_op, part_side) and every
+// plan_* function are private to this unit; the sequence path (host_seq.cpp) enters through want_partitioned,
+// partitioned_insert, partitioned_contains, want_partitioned_query and split_contains (host_internal.hpp).  The
+// scratch lives in the filter's three DevScratch buffers.  Kernels: partition_kernels.hip, part_hash_inst.hip.
 #include "../../include/btlbf.h"
 #include "internal.hpp"
 #include "host_internal.hpp"
@@ -22,7 +24,6 @@ namespace {
 // partitioned query: room for the failed positions of one batch and their hash set
 static constexpr uint64_t kFailCap = 4ull << 20;          // entries
 static constexpr uint64_t kFailTableSlots = 2 * kFailCap; // power of two
-static constexpr uint64_t kFailBytes = 256 + kFailCap * 8 + kFailTableSlots * 8;
 // entries a FRESH insert batch (partitioned_insert) may report as explicit positions instead of staging them
 static constexpr uint64_t kFreshSpillCap = 16ull << 20;
 
@@ -72,6 +73,8 @@ struct PartPlan {
 	// round parity (part_hash_inst.hip): [regions][2][late_cap] words behind the tail of the scratch
 	uint32_t* late_buf = nullptr;
 	uint32_t late_cap = 0;
+	// level-0 bins that are split and applied together, of the n_bins0 a pass has (plans without groups: all of them)
+	uint32_t group(uint32_t n_bins0) const { return n_levels >= 2 && group_bins ? group_bins : n_bins0; }
 };
 
 // chunks a region needs for `mean_entries` expected entries (Poisson: mean + 8 sigma) plus the
@@ -210,30 +213,6 @@ uint8_t* carve_levels(PartPlan& pl, uint8_t* p, int first_level)
 	return p;
 }
 
-int ensure_scratch(btlbf_filter* f, uint64_t bytes, bool* ok)
-{
-	*ok = true;
-	if (bytes <= f->part_bytes)
-		return BTLBF_OK;
-	(void)hipFree(f->d_part);
-	f->d_part = nullptr;
-	f->part_bytes = 0;
-	hipError_t e = hipMalloc(&f->d_part, bytes);
-	if (e != hipSuccess) { // parked staging buffers of HOST-mode calls may be what is missing
-		(void)hipGetLastError();
-		dev_pool().drain(f->device);
-		e = hipMalloc(&f->d_part, bytes);
-	}
-	if (e != hipSuccess) {
-		(void)hipGetLastError();
-		f->d_part = nullptr;
-		*ok = false; // no room for scratch: the caller falls back to the direct kernels
-		return BTLBF_OK;
-	}
-	f->part_bytes = bytes;
-	return BTLBF_OK;
-}
-
 uint64_t scratch_budget(btlbf_filter* f)
 {
 	if (f->part_budget)
@@ -241,7 +220,7 @@ uint64_t scratch_budget(btlbf_filter* f)
 	size_t free_b = 0, total_b = 0;
 	if (hipMemGetInfo(&free_b, &total_b) != hipSuccess)
 		return 0;
-	return (uint64_t)((double)(free_b + f->part_bytes) * 0.80);
+	return (uint64_t)((double)(free_b + f->part.bytes) * 0.80);
 }
 
 unsigned cu_count(int device)
@@ -264,13 +243,25 @@ double probes_per_tile(const btlbf_filter* f, const PartTiling& tl)
 	return tl.windows_per_tile * f->hp.h + 1.0;
 }
 
-// how level-0 bins map to positions, for the kernels (PartSide::bin_wseg)
-void side_bins(PartSide& sd, const PartPlan& pl)
+// The side block of a pass over f's array: what the filter fixes (bits or counters, the threshold of a counting query,
+// the base of the positions a pass reports) and, for a pass A planned here, its late images and how level-0 bins map
+// to positions (PartSide::bin_wseg).  The fail, spill and fresh fields are the caller's.
+PartSide part_side(const btlbf_filter* f, const PartPlan* pl = nullptr)
 {
-	sd.bin_wseg = pl.lv[0].wseg;
-	sd.bin_magic = pl.lv[0].wseg ? (uint32_t)(((1ull << 32) + pl.lv[0].wseg - 1) / pl.lv[0].wseg) : 0;
-	sd.bin_seg_shift = pl.seg_shift;
-	sd.bin_width = pl.lv[0].wseg << pl.seg_shift;
+	PartSide sd;
+	memset(&sd, 0, sizeof sd);
+	sd.pos_base = f->mod.shard_lo;
+	sd.counting = f->kind == BTLBF_COUNTING8;
+	sd.threshold = f->thr;
+	if (pl) {
+		sd.late_buf = pl->late_buf;
+		sd.late_cap = pl->late_cap;
+		sd.bin_wseg = pl->lv[0].wseg;
+		sd.bin_magic = pl->lv[0].wseg ? (uint32_t)(((1ull << 32) + pl->lv[0].wseg - 1) / pl->lv[0].wseg) : 0;
+		sd.bin_seg_shift = pl->seg_shift;
+		sd.bin_width = pl->lv[0].wseg << pl->seg_shift;
+	}
+	return sd;
 }
 
 // run the split levels lv[1..] over the level-0 data `in0`, then the apply / test pass
@@ -288,7 +279,7 @@ int run_levels(btlbf_filter* f, PartPlan& pl, PartIn in0, const PartSide& sd, in
 		n_bins0 = pl.lv[0].bins - bin_offset;
 	// group by group: split the group's level-0 bins all the way down, then apply its segments
 	// (plans without groups: one group of everything)
-	const uint32_t group = pl.n_levels >= 2 && pl.group_bins ? pl.group_bins : n_bins0;
+	const uint32_t group = pl.group(n_bins0);
 	for (uint32_t b0 = 0; b0 < n_bins0; b0 += group) {
 		PartIn in = in0;
 		uint32_t first_in = b0, abs_first = bin_offset + b0, n_in = std::min(group, n_bins0 - b0);
@@ -322,17 +313,34 @@ constexpr double kAutoInsertRatio = 0.0095, kAutoQueryRatio = 0.0165;
 // plan_level0: calls of this many probes or more (4x10^9 k-mers at h = 4) take 256 level-0 bins where 512 are the rule
 constexpr double kWideSplitProbes = 1.6e10;
 
-// the segment size and the level-0 bins (pass A's output) of this filter's local array; false = no partitioned path
-// probes a call over `len` bases sends to this filter's local array (a shard keeps its window's share) -- or, with a
-// scratch budget imposed by the caller, what one batch of that budget holds (about 5.5 bytes of scratch per probe): the
-// figure plan_level0's batch-size rule goes by.  (Deterministic on purpose: the split query plans twice and both plans
-// must agree; the free-memory budget would not be the same figure twice.)
+// probes a call over `len` bases sends to this filter's local array (a shard keeps its window's share)
+double local_probes(const btlbf_filter* f, uint64_t len)
+{
+	return (double)len * f->hp.h * ((double)f->mod.shard_len / (double)f->mod.size);
+}
+
+// are `probes` worth a sweep of the local array?  `ratio`: AUTO's break-even in probes per byte of it; and the batch
+// must be big enough to be worth the five launches of a sweep
+bool worth_sweep(const btlbf_filter* f, double probes, double ratio)
+{
+	return probes >= ratio * (double)f->local_bytes && probes >= 4.0e6;
+}
+
+// the direct kernel that answers contains() for this filter
+int direct_query_op(const btlbf_filter* f)
+{
+	return f->kind == BTLBF_COUNTING8 ? OP_CBF_QUERY : f->shard_count != 1 ? OP_BF_CONTAINS_WIN : OP_BF_CONTAINS;
+}
+
+// local_probes -- or, with a scratch budget imposed by the caller, what one batch of that budget holds (about 5.5 bytes
+// of scratch per probe): the figure plan_level0's batch-size rule goes by
 double call_probes(const btlbf_filter* f, uint64_t len)
 {
-	const double all = (double)len * f->hp.h * ((double)f->mod.shard_len / (double)f->mod.size);
+	const double all = local_probes(f, len);
 	return f->part_budget ? std::min(all, (double)f->part_budget / 5.5) : all;
 }
 
+// the segment size and the level-0 bins (pass A's output) of this filter's local array; false = no partitioned path
 // `call_probes`: probes of the whole call (0 = unknown), for the one choice that depends on the batch size
 bool plan_level0(const btlbf_filter* f, PartPlan& pl, double call_probes = 0)
 {
@@ -378,28 +386,39 @@ bool plan_level0(const btlbf_filter* f, PartPlan& pl, double call_probes = 0)
 	return true;
 }
 
-// plan the single-GPU pipeline for a buffer and (re)allocate the scratch;
-// *ok = false means "not applicable, use the direct kernel"
-int part_prepare(btlbf_filter* f, const SeqArgs& base, PartTail* tail, PartPlan& pl, PartTiling* tiling,
-                 uint8_t** extra, bool* ok, int mode, double auto_ratio)
+// what part_prepare makes of a buffer
+struct PartPrep {
+	PartPlan pl;
+	PartTiling tiling{};
+	PartTail tail{};
+	uint8_t* extra = nullptr; // the tail's place in the scratch
+	bool ok = false;          // false = not applicable, use the direct kernel
+};
+
+// plan the single-GPU pipeline for a buffer and (re)allocate the scratch; `level0`: the caller's plan_level0 of this
+// very buffer, where it has made one already (the split query)
+PartPrep part_prepare(btlbf_filter* f, const SeqArgs& base, int mode, double auto_ratio, const PartPlan* level0 = nullptr)
 {
-	*ok = false;
-	if (!plan_level0(f, pl, call_probes(f, base.len)))
-		return BTLBF_OK;
+	PartPrep pp;
+	PartPlan& pl = pp.pl;
+	if (level0)
+		pl = *level0;
+	else if (!plan_level0(f, pl, call_probes(f, base.len)))
+		return pp;
 	PartLevel& l0 = pl.lv[0];
 	l0.regions = cu_count(f->device); // pass-A workgroups: one per CU
 	if (!plan_splits(pl, l0.regions, cu_count(f->device)) || !part_hash_fits(f->hp, l0.P))
-		return BTLBF_OK;
-	*tiling = part_tiling(f->hp, l0.P, base.layout, base.len);
+		return pp;
+	pp.tiling = part_tiling(f->hp, l0.P, base.layout, base.len);
 	const uint64_t budget = scratch_budget(f);
-	*tail = part_tail(budget);
+	pp.tail = part_tail(budget);
 	// (a caller-imposed budget below 2 GiB keeps its scratch for the entries: pass A then runs its plain schedule)
 	pl.late_cap = budget >= (2ull << 30) ? part_late_cap() : 0;
 	const uint64_t late_bytes = (uint64_t)l0.regions * 2 * pl.late_cap * sizeof(uint32_t);
-	const uint64_t extra_bytes = ((tail->bytes + 255) / 256) * 256 + late_bytes;
+	const uint64_t extra_bytes = ((pp.tail.bytes + 255) / 256) * 256 + late_bytes;
 	// a shard fed every rank's reads (ShardedBloomFilter's gather mode) keeps only its window's share
-	const double ppt = probes_per_tile(f, *tiling) * ((double)f->mod.shard_len / (double)f->mod.size);
-	uint64_t tiles = tiling->n_tiles;
+	const double ppt = probes_per_tile(f, pp.tiling) * ((double)f->mod.shard_len / (double)f->mod.size);
+	uint64_t tiles = pp.tiling.n_tiles;
 	for (int iter = 0; iter < 64; ++iter) {
 		plan_caps(pl, (double)tiles_for_caps(tiles, l0.regions) * ppt, 0);
 		pl.bytes_total += extra_bytes;
@@ -410,43 +429,19 @@ int part_prepare(btlbf_filter* f, const SeqArgs& base, PartTail* tail, PartPlan&
 		tiles = nt >= tiles ? tiles - 1 : (nt ? nt : 1);
 	}
 	if (pl.bytes_total > budget)
-		return BTLBF_OK;
+		return pp;
 	// AUTO: a batch that the scratch budget has cut small is not worth a sweep of the array either (the rule
 	// want_partitioned applies to the whole call, applied to one batch): a filter that nearly fills the HBM
 	// leaves a few GB for scratch, and the direct kernels are then the faster path
-	if (mode == BTLBF_INSERT_AUTO && tiles < tiling->n_tiles && (double)tiles * ppt < auto_ratio * (double)f->local_bytes)
-		return BTLBF_OK;
+	if (mode == BTLBF_INSERT_AUTO && tiles < pp.tiling.n_tiles && (double)tiles * ppt < auto_ratio * (double)f->local_bytes)
+		return pp;
 	pl.tiles_per_batch = tiles;
-	int rc = ensure_scratch(f, pl.bytes_total, ok);
-	if (rc || !*ok)
-		return rc;
-	*extra = carve_levels(pl, static_cast<uint8_t*>(f->d_part), 0);
-	pl.late_buf = pl.late_cap ? reinterpret_cast<uint32_t*>(*extra + ((tail->bytes + 255) / 256) * 256) : nullptr;
-	return BTLBF_OK;
-}
-
-// hit_bits := hit_bits with the windows owning a failed position cleared, for seq tiles
-// [first, first+n) of the direct kernels' tiling
-int resolve_range(btlbf_filter* f, const SeqArgs& base, uint8_t* hit_bits, const uint64_t* fail_list, uint64_t n_fail,
-                  uint64_t* table, uint64_t max_slots, uint64_t first, uint64_t n, hipStream_t s)
-{
-	SeqArgs d = base;
-	d.first_tile = first;
-	d.n_tiles = n;
-	d.hit_bits = hit_bits;
-	d.valid_bits = nullptr;
-	d.counts = nullptr;
-	// the table is sized to the set (load <= 1/4): a few thousand failed positions make a table that stays in
-	// L2, and every probe of every window of the range is looked up in it
-	uint64_t slots = 1024;
-	while (slots < 4 * n_fail && slots < max_slots)
-		slots <<= 1;
-	HIP_TRY(hipMemsetAsync(table, 0, slots * 8, s));
-	HIP_TRY(launch_failset_build(fail_list, n_fail, table, slots - 1, s));
-	d.buckets = table;
-	d.bucket_cap = slots - 1;
-	HIP_TRY(launch_seq_op(OP_BF_RESOLVE, d, s));
-	return BTLBF_OK;
+	if (!f->part.grow(pl.bytes_total, f->device))
+		return pp; // no room for scratch: the caller falls back to the direct kernels
+	pp.extra = carve_levels(pl, static_cast<uint8_t*>(f->part.p), 0);
+	pl.late_buf = pl.late_cap ? reinterpret_cast<uint32_t*>(pp.extra + ((pp.tail.bytes + 255) / 256) * 256) : nullptr;
+	pp.ok = true;
+	return pp;
 }
 
 // ---- multi-GPU routing (SURVEY.md 8e on the partitioned pipeline) -------------------------------------
@@ -464,6 +459,7 @@ struct RoutePlan {
 	uint32_t regions = 0;
 	uint32_t cap = 0;
 	uint64_t ent_bytes_per_shard = 0, cnt_bytes_per_shard = 0;
+	PartPlan owner; // the owner's levels below the level-0 bins of its shard (plan_routed with want_owner)
 };
 
 // An entry is the offset of a position inside its level-0 bin and has 32 bits; pass A stages at most 1024
@@ -544,6 +540,50 @@ LayoutParams layout_params(const btlbf_layout* layout)
 	return lay;
 }
 
+// the plan of a routed pass, made once per call: the exchange geometry and, for `want_owner`, the owner's levels below
+// it for blocks of n_blocks origins (0: of every shard)
+int plan_routed(btlbf_filter* f, uint64_t plan_len, const LayoutParams& lay, unsigned n_shards, unsigned n_blocks,
+                bool want_owner, RoutePlan& rp)
+{
+	if (!f)
+		return fail(BTLBF_EINVAL, "null argument");
+	int rc = route_plan(f, plan_len, lay, n_shards, rp);
+	if (rc || !want_owner)
+		return rc;
+	return owner_plan(f, rp, lay, plan_len, n_blocks ? n_blocks : n_shards, n_shards, rp.owner);
+}
+
+// the owner's passes over level-0 bins [first_bin, first_bin + n_bins) of blocks routed with `rp`
+int apply_routed(btlbf_filter* f, RoutePlan& rp, const void* recv_ent, const void* recv_cnt, unsigned n_blocks,
+                 unsigned first_bin, unsigned n_bins, unsigned n_shards, int query, uint64_t* fail_list, uint64_t fail_cap,
+                 uint64_t* fail_count, void* stream)
+{
+	PartPlan& pl = rp.owner;
+	if (!recv_ent || !recv_cnt || n_blocks == 0)
+		return fail(BTLBF_EINVAL, "null argument");
+	if (f->shard_count != n_shards)
+		return fail(BTLBF_EINVAL, "filter is shard %u of %u, not of %u", f->shard_index, f->shard_count, n_shards);
+	if (query && (!fail_list || !fail_count))
+		return fail(BTLBF_EINVAL, "query needs a fail list");
+	const uint32_t group = pl.group(rp.bins_per_shard);
+	if (n_bins == 0 || first_bin + n_bins > rp.bins_per_shard || first_bin % group || (n_bins % group && first_bin + n_bins != rp.bins_per_shard))
+		return fail(BTLBF_EINVAL, "bins [%u, +%u) are not whole groups of %u of this shard's %u level-0 bins", first_bin,
+		            n_bins, group, rp.bins_per_shard);
+	DeviceGuard g(f->device);
+	hipStream_t s = static_cast<hipStream_t>(stream);
+	MATERIALIZE(f, s);
+	if (!f->part.grow(pl.bytes_total, f->device))
+		return fail(BTLBF_ENOMEM, "no room for %llu bytes of partition scratch", (unsigned long long)pl.bytes_total);
+	carve_levels(pl, static_cast<uint8_t*>(f->part.p), 1);
+	PartSide sd = part_side(f); // incrementAll / counter >= threshold at the owner
+	sd.fail_list = fail_list;
+	sd.fail_count = reinterpret_cast<unsigned long long*>(fail_count);
+	sd.fail_cap = fail_cap;
+	PartIn in0{n_blocks, n_bins, rp.regions, rp.cap, static_cast<const uint32_t*>(recv_cnt),
+	           static_cast<const uint32_t*>(recv_ent)};
+	return run_levels(f, pl, in0, sd, query, s, first_bin, n_bins);
+}
+
 } // namespace
 
 namespace btlbf {
@@ -564,8 +604,7 @@ bool want_partitioned(const btlbf_filter* f, uint64_t len, int counting_op)
 	// auto: one sweep of the local array (read + write) must be cheaper than the random atomics it
 	// replaces: ~ 2*bytes/5.8e12 s against probes/21e9 s (kAutoInsertRatio); and the batch must be big
 	// enough to be worth five launches
-	const double probes = (double)len * f->hp.h * ((double)f->mod.shard_len / (double)f->mod.size);
-	return probes >= kAutoInsertRatio * (double)f->local_bytes && probes >= 4.0e6;
+	return worth_sweep(f, local_probes(f, len), kAutoInsertRatio);
 }
 
 int partitioned_insert(btlbf_filter* f, const SeqArgs& base, hipStream_t s, bool* done)
@@ -576,41 +615,31 @@ int partitioned_insert(btlbf_filter* f, const SeqArgs& base, hipStream_t s, bool
 	// the overflow paths of passes A and B write straight into the array, so a fresh batch reports those entries
 	// as explicit positions instead (as the multi-GPU routing does) and they are applied after its last pass C;
 	// more of them than the list holds (heavily skewed input) and the batch is redone the ordinary way.
-	PartPlan pl;
-	PartTiling tiling;
-	uint8_t* extra = nullptr;
-	bool ok = false;
-	PartTail tail;
-	int rc = part_prepare(f, base, &tail, pl, &tiling, &extra, &ok, f->insert_mode, kAutoInsertRatio);
-	if (rc || !ok)
-		return rc;
-	const uint64_t total_tiles = tiling.n_tiles;
+	PartPrep pp = part_prepare(f, base, f->insert_mode, kAutoInsertRatio);
+	if (!pp.ok)
+		return BTLBF_OK;
+	PartPlan& pl = pp.pl;
+	const uint64_t total_tiles = pp.tiling.n_tiles;
 	for (uint64_t t0 = 0; t0 < total_tiles; t0 += pl.tiles_per_batch) {
 		SeqArgs a = base;
 		a.first_tile = t0;
 		a.n_tiles = std::min<uint64_t>(pl.tiles_per_batch, total_tiles - t0);
 		for (int attempt = 0; attempt < 2; ++attempt) {
 			const bool fresh = f->lazy_zero;
-			PartSide sd;
-			memset(&sd, 0, sizeof sd);
-			sd.counting = f->kind == BTLBF_COUNTING8;
-			sd.late_buf = pl.late_buf;
-			sd.late_cap = pl.late_cap;
-			side_bins(sd, pl);
+			PartSide sd = part_side(f, &pl);
 			if (fresh) {
 				HIP_TRY(order_after_clear(f, s)); // this batch IS the clear: after the point it was asked for
 				sd.fresh = 1;
-				sd.pos_base = f->mod.shard_lo;
-				sd.spill_count = reinterpret_cast<unsigned long long*>(extra);
-				sd.spill_list = reinterpret_cast<uint64_t*>(extra + 256);
-				sd.spill_cap = tail.spill_cap;
+				sd.spill_count = reinterpret_cast<unsigned long long*>(pp.extra);
+				sd.spill_list = reinterpret_cast<uint64_t*>(pp.extra + 256);
+				sd.spill_cap = pp.tail.spill_cap;
 				HIP_TRY(hipMemsetAsync(sd.spill_count, 0, 8, s));
 			}
 			{
 				ProfSpan ps(f, BTLBF_PROF_INSERT_HASH, s);
 				HIP_TRY(launch_part_hash(a, pl.lv[0].out(), pl.lv[0].shift, sd, 0, s));
 			}
-			if ((rc = run_levels(f, pl, pl.lv[0].in(), sd, 0, s)))
+			if (int rc = run_levels(f, pl, pl.lv[0].in(), sd, 0, s))
 				return rc;
 			if (!fresh)
 				break;
@@ -619,11 +648,8 @@ int partitioned_insert(btlbf_filter* f, const SeqArgs& base, hipStream_t s, bool
 			hipError_t e = hipMemcpyAsync(&n_spill, sd.spill_count, 8, hipMemcpyDeviceToHost, s);
 			if (e == hipSuccess)
 				e = hipStreamSynchronize(s);
-			if (e == hipSuccess && n_spill <= tail.spill_cap) {
-				PartSide plain;
-				memset(&plain, 0, sizeof plain);
-				plain.counting = sd.counting;
-				e = launch_spill(f->d_data, sd.spill_list, n_spill, f->mod.shard_lo, f->mod.shard_len, 0, plain, s);
+			if (e == hipSuccess && n_spill <= pp.tail.spill_cap) {
+				e = launch_spill(f->d_data, sd.spill_list, n_spill, f->mod.shard_lo, f->mod.shard_len, 0, part_side(f), s);
 				if (e == hipSuccess)
 					break;
 			}
@@ -646,33 +672,23 @@ int partitioned_insert(btlbf_filter* f, const SeqArgs& base, hipStream_t s, bool
 // hit_bits (device) is required; valid_bits and counts are optional.
 // base.read_mask (the split query): those reads are left out -- no bits, no counts; defer_hit_count: counts[1] is left
 // for the caller, who adds the left-out reads' answers to the bitmap first.
-int partitioned_contains(btlbf_filter* f, const SeqArgs& base, uint8_t* hit_bits, uint8_t* valid_bits,
-                         uint64_t* counts, hipStream_t s, bool* done, bool defer_hit_count)
+// `level0`: see part_prepare
+static int part_query(btlbf_filter* f, const SeqArgs& base, uint8_t* hit_bits, uint8_t* valid_bits, uint64_t* counts,
+               hipStream_t s, bool* done, bool defer_hit_count, const PartPlan* level0)
 {
 	*done = false;
-	PartPlan pl;
-	PartTiling tiling;
-	uint8_t* extra = nullptr;
-	bool ok = false;
-	PartTail tail;
-	int rc = part_prepare(f, base, &tail, pl, &tiling, &extra, &ok, f->query_mode, kAutoQueryRatio);
-	if (rc || !ok)
-		return rc;
-	const uint64_t total_tiles = tiling.n_tiles;
-	PartSide sd;
-	memset(&sd, 0, sizeof sd);
-	sd.fail_count = reinterpret_cast<unsigned long long*>(extra);
-	sd.fail_list = reinterpret_cast<uint64_t*>(extra + 256);
-	sd.fail_cap = tail.fail_cap;
-	sd.counting = f->kind == BTLBF_COUNTING8;
-	sd.threshold = f->thr;
-	sd.late_buf = pl.late_buf;
-	sd.late_cap = pl.late_cap;
-	side_bins(sd, pl);
-	sd.pos_base = f->mod.shard_lo; // the fail set is keyed by global position
-	const int direct_op = sd.counting ? OP_CBF_QUERY : f->shard_count != 1 ? OP_BF_CONTAINS_WIN : OP_BF_CONTAINS;
-	uint64_t* table = sd.fail_list + tail.fail_cap;
-	uint64_t* ctl = reinterpret_cast<uint64_t*>(extra + 64); // two words of stream-side control next to the fail count
+	PartPrep pp = part_prepare(f, base, f->query_mode, kAutoQueryRatio, level0);
+	if (!pp.ok)
+		return BTLBF_OK;
+	PartPlan& pl = pp.pl;
+	const uint64_t total_tiles = pp.tiling.n_tiles;
+	PartSide sd = part_side(f, &pl); // (pos_base: the fail set is keyed by global position)
+	sd.fail_count = reinterpret_cast<unsigned long long*>(pp.extra);
+	sd.fail_list = reinterpret_cast<uint64_t*>(pp.extra + 256);
+	sd.fail_cap = pp.tail.fail_cap;
+	const int direct_op = direct_query_op(f);
+	uint64_t* table = sd.fail_list + pp.tail.fail_cap;
+	uint64_t* ctl = reinterpret_cast<uint64_t*>(pp.extra + 64); // two words of stream-side control next to the fail count
 	if (counts)
 		HIP_TRY(hipMemsetAsync(counts, 0, 16, s));
 	const uint64_t seq_tw = (uint64_t)seq_tile_windows();
@@ -689,7 +705,7 @@ int partitioned_contains(btlbf_filter* f, const SeqArgs& base, uint8_t* hit_bits
 			ProfSpan ps(f, BTLBF_PROF_QUERY_HASH, s);
 			HIP_TRY(launch_part_hash(a, pl.lv[0].out(), pl.lv[0].shift, sd, 1, s));
 		}
-		if ((rc = run_levels(f, pl, pl.lv[0].in(), sd, 1, s)))
+		if (int rc = run_levels(f, pl, pl.lv[0].in(), sd, 1, s))
 			return rc;
 		// redo / refine this batch's window range with the direct kernels: their tiles that overlap the
 		// batch's bytes.  A tile more at either end is harmless: a failed position is a bit that IS clear,
@@ -697,11 +713,11 @@ int partitioned_contains(btlbf_filter* f, const SeqArgs& base, uint8_t* hit_bits
 		// What happens is decided on the device (GATE_*): no failed position -> nothing; up to fail_cap -> they become
 		// a hash set and one hashing pass clears the windows that own one; more -> the range is redone by the direct
 		// kernel.  All launches are issued, the ones decided against return at once: no host round trip per batch.
-		const uint64_t first = t0 * tiling.tile_bytes / seq_tw;
-		const uint64_t end_b = std::min<uint64_t>(base.len, (t0 + a.n_tiles) * (uint64_t)tiling.tile_bytes);
+		const uint64_t first = t0 * pp.tiling.tile_bytes / seq_tw;
+		const uint64_t end_b = std::min<uint64_t>(base.len, (t0 + a.n_tiles) * (uint64_t)pp.tiling.tile_bytes);
 		const uint64_t n = std::min<uint64_t>((end_b + seq_tw - 1) / seq_tw, seq_tiles_all) - first;
 		ProfSpan ps(f, BTLBF_PROF_QUERY_RESOLVE, s);
-		HIP_TRY(launch_failset_auto(sd.fail_list, sd.fail_count, tail.fail_cap, table, tail.table_slots, ctl, s));
+		HIP_TRY(launch_failset_auto(sd.fail_list, sd.fail_count, pp.tail.fail_cap, table, pp.tail.table_slots, ctl, s));
 		SeqArgs d = base;
 		d.first_tile = first;
 		d.n_tiles = n;
@@ -723,6 +739,12 @@ int partitioned_contains(btlbf_filter* f, const SeqArgs& base, uint8_t* hit_bits
 	return BTLBF_OK;
 }
 
+int partitioned_contains(btlbf_filter* f, const SeqArgs& base, uint8_t* hit_bits, uint8_t* valid_bits,
+                         uint64_t* counts, hipStream_t s, bool* done, bool defer_hit_count)
+{
+	return part_query(f, base, hit_bits, valid_bits, counts, s, done, defer_hit_count, nullptr);
+}
+
 // AUTO decision for contains(): large batch, and a sample of tiles says nearly every k-mer hits
 int want_partitioned_query(btlbf_filter* f, const SeqArgs& base, hipStream_t s, bool* yes)
 {
@@ -735,8 +757,8 @@ int want_partitioned_query(btlbf_filter* f, const SeqArgs& base, hipStream_t s, 
 		*yes = true;
 		return BTLBF_OK;
 	}
-	const double live = (double)base.len * f->hp.h * ((double)f->mod.shard_len / (double)f->mod.size);
-	if (live < kAutoQueryRatio * (double)f->local_bytes || live < 4.0e6)
+	const double live = local_probes(f, base.len);
+	if (!worth_sweep(f, live, kAutoQueryRatio))
 		return BTLBF_OK;
 	// sample 64 tiles spread over the buffer with the direct kernel
 	const uint64_t tiles = (base.len + seq_tile_windows() - 1) / seq_tile_windows();
@@ -750,10 +772,7 @@ int want_partitioned_query(btlbf_filter* f, const SeqArgs& base, hipStream_t s, 
 		a.valid_bits = nullptr;
 		a.counts = reinterpret_cast<uint64_t*>(f->d_scalar);
 		a.min_out = nullptr;
-		HIP_TRY(launch_seq_op(f->kind == BTLBF_COUNTING8 ? OP_CBF_QUERY
-		                      : f->shard_count != 1      ? OP_BF_CONTAINS_WIN
-		                                                 : OP_BF_CONTAINS,
-		                      a, s));
+		HIP_TRY(launch_seq_op(direct_query_op(f), a, s));
 	}
 	unsigned long long c[2] = {0, 0};
 	HIP_TRY(hipMemcpyAsync(c, f->d_scalar, 16, hipMemcpyDeviceToHost, s));
@@ -767,12 +786,36 @@ int want_partitioned_query(btlbf_filter* f, const SeqArgs& base, hipStream_t s, 
 	return BTLBF_OK;
 }
 
-// contains() over fixed-length reads in AUTO mode (aux_kernels.hip, "split query"): sample every read; if the
-// misses are few enough for the fail list the whole buffer goes partitioned (*decided = 2), if hardly anything
-// hits it goes to the gather kernel (1); otherwise the reads are compacted into a warm and a cold buffer, the
-// warm one takes the partitioned path, the cold one the early-exit gather kernel, and the two bitmaps are
-// merged back into the caller's layout (3: a.hit_bits / a.valid_bits / a.counts are complete).
-int split_contains(btlbf_filter* f, const SeqArgs& a, int direct_op, hipStream_t s, int* decided)
+// ---- the split query: contains() over fixed-length reads in AUTO mode (aux_kernels.hip) ------------------------------
+// what its steps share: the reads' cold flags and their prefix sums (in f->flags) and the counts
+struct SplitState {
+	uint32_t L = 0; // read length
+	uint64_t n_reads = 0;
+	unsigned long long n_cold = 0, *d_ncold = nullptr;
+	uint64_t* d_flags = nullptr;
+	uint32_t* d_prefix = nullptr;
+};
+
+static uint64_t up256(uint64_t x) { return (x + 255) / 256 * 256; }
+
+// the direct kernel over a compacted buffer of the split query: it ADDS its clean windows and its hits to a.counts
+static int split_direct(btlbf_filter* f, const SeqArgs& a, int direct_op, const uint8_t* seq, uint64_t len, uint8_t* hit_bits,
+                        uint8_t* valid_bits, hipStream_t s)
+{
+	SeqArgs d = a;
+	d.seq = seq;
+	d.len = len;
+	d.hit_bits = hit_bits;
+	d.valid_bits = valid_bits;
+	ProfSpan ps(f, BTLBF_PROF_QUERY_DIRECT, s);
+	REQUIRE_MATERIALIZED(f);
+	HIP_TRY(launch_seq_op(direct_op, d, s));
+	return BTLBF_OK;
+}
+
+// The decision: sample the reads; *decided = 0: not applicable (the plain paths decide, want_partitioned_query), 1: the
+// gather kernel, 2: the whole buffer goes partitioned, 3: split -- `st` then holds every read's flag and the cold count.
+static int split_decide(btlbf_filter* f, const SeqArgs& a, hipStream_t s, SplitState& st, int* decided)
 {
 	*decided = 0;
 	const uint32_t L = a.layout.starts ? 0 : a.layout.read_len, k = f->hp.k;
@@ -784,68 +827,50 @@ int split_contains(btlbf_filter* f, const SeqArgs& a, int direct_op, hipStream_t
 		return BTLBF_OK;
 	const uint64_t n_reads = a.len / L;
 	const uint32_t W = L - k + 1;
-	const double live = (double)n_reads * W * f->hp.h;
-	if (live < kAutoQueryRatio * (double)f->local_bytes || live < 4.0e6 || n_reads >= (1ull << 32))
+	if (!worth_sweep(f, (double)n_reads * W * f->hp.h, kAutoQueryRatio) || n_reads >= (1ull << 32))
 		return BTLBF_OK; // small batches: the direct kernel (want_partitioned_query agrees)
 	const uint64_t n_fw = (n_reads + 63) / 64;
-	// temporaries are cached in the filter (grow-only, btlbf_release_scratch returns them): hipMalloc / hipFree
-	// of tens of GB cost more than the kernels.  The small one (flags, prefix sums) is needed by every call;
+	// temporaries are cached in the filter (DevScratch): the small one (flags, prefix sums) is needed by every call,
 	// the large one (compacted reads, their bitmaps) only once the split path is taken
-	auto up = [](uint64_t x) { return (x + 255) / 256 * 256; };
-	auto grow = [](void** p, uint64_t* have, uint64_t bytes) -> bool {
-		if (bytes <= *have)
-			return true;
-		(void)hipFree(*p);
-		*p = nullptr;
-		*have = 0;
-		if (hipMalloc(p, bytes) != hipSuccess) {
-			(void)hipGetLastError();
-			return false;
-		}
-		*have = bytes;
-		return true;
-	};
 	// (the flags are readable for 256 bytes behind their last word: pass A reads up to 34 words from a tile's first one on)
-	const uint64_t sz_flags = up(n_fw * 8 + 256), sz_prefix = up((n_fw + (n_fw + 1023) / 1024 + 1) * 4);
-	if (!grow(&f->d_flags, &f->flags_bytes, 256 + sz_flags + sz_prefix))
+	const uint64_t sz_flags = up256(n_fw * 8 + 256), sz_prefix = up256((n_fw + (n_fw + 1023) / 1024 + 1) * 4);
+	if (!f->flags.grow(256 + sz_flags + sz_prefix, f->device))
 		return BTLBF_OK; // no room: the plain paths decide (want_partitioned_query)
-	unsigned long long* d_ncold = static_cast<unsigned long long*>(f->d_flags);
-	uint64_t* d_flags = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(f->d_flags) + 256);
-	uint32_t* d_prefix = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(f->d_flags) + 256 + sz_flags);
-	unsigned long long n_cold = 0;
-	auto sample = [&](uint32_t stride, uint32_t probes2) -> int {
-		HIP_TRY(hipMemsetAsync(d_ncold, 0, 8, s));
-		{
-			ProfSpan ps(f, BTLBF_PROF_QUERY_RESOLVE, s);
-			HIP_TRY(launch_read_sample(a.seq, n_reads, L, stride, f->hp, f->mod, f->d_data, f->kind == BTLBF_COUNTING8,
-			                           f->thr, d_flags, reinterpret_cast<uint64_t*>(d_ncold), s, probes2));
-		}
-		HIP_TRY(hipMemcpyAsync(&n_cold, d_ncold, 8, hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		return BTLBF_OK;
-	};
+	uint8_t* const base = static_cast<uint8_t*>(f->flags.p);
+	st.L = L;
+	st.n_reads = n_reads;
+	st.d_ncold = reinterpret_cast<unsigned long long*>(base);
+	st.d_flags = reinterpret_cast<uint64_t*>(base + 256);
+	st.d_prefix = reinterpret_cast<uint32_t*>(base + 256 + sz_flags);
 	// what the fail list copes with / what is worth a sweep of the array, in reads
 	// (the list the partitioned path will really have: a small scratch budget gets a short one, part_tail)
 	const double few_cold = 0.25 * (double)part_tail(scratch_budget(f)).fail_cap / ((double)W * f->hp.h);
-	auto warm_too_few = [&](double n_warm_reads) {
-		const double wl = n_warm_reads * W * f->hp.h;
-		return wl < kAutoQueryRatio * (double)f->local_bytes || wl < 4.0e6;
+	auto sample = [&](uint32_t stride, uint32_t probes2) -> int { // flags and st.n_cold from every stride-th read
+		HIP_TRY(hipMemsetAsync(st.d_ncold, 0, 8, s));
+		{
+			ProfSpan ps(f, BTLBF_PROF_QUERY_RESOLVE, s);
+			HIP_TRY(launch_read_sample(a.seq, n_reads, L, stride, f->hp, f->mod, f->d_data, f->kind == BTLBF_COUNTING8,
+			                           f->thr, st.d_flags, reinterpret_cast<uint64_t*>(st.d_ncold), s, probes2));
+		}
+		HIP_TRY(hipMemcpyAsync(&st.n_cold, st.d_ncold, 8, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		return BTLBF_OK;
 	};
+	auto warm_too_few = [&](double n_warm_reads) { return !worth_sweep(f, n_warm_reads * W * f->hp.h, kAutoQueryRatio); };
 	// 1. an estimate from one read in 64: all-hit and all-miss buffers -- the common cases -- are recognised at
 	//    1/64 of the cost of looking at every read
-	int rc;
 	const uint32_t stride = n_reads >= (1u << 20) ? 64 : 1;
 	double cold_frac = 1.0; // estimate from the first look (unknown: assume many)
 	if (stride > 1) {
-		if ((rc = sample(stride, 0)))
+		if (int rc = sample(stride, 0))
 			return rc;
-		cold_frac = (double)n_cold / (double)((n_reads + stride - 1) / stride);
 		const uint64_t n_s = (n_reads + stride - 1) / stride;
-		if (n_cold == 0 && (double)n_reads * 8.0 / (double)n_s < few_cold) { // none in the sample: few overall
+		cold_frac = (double)st.n_cold / (double)n_s;
+		if (st.n_cold == 0 && (double)n_reads * 8.0 / (double)n_s < few_cold) { // none in the sample: few overall
 			*decided = 2;
 			return BTLBF_OK;
 		}
-		if (warm_too_few((double)(n_s - n_cold) * stride * 1.5)) {
+		if (warm_too_few((double)(n_s - st.n_cold) * stride * 1.5)) {
 			*decided = 1;
 			return BTLBF_OK;
 		}
@@ -855,128 +880,115 @@ int split_contains(btlbf_filter* f, const SeqArgs& a, int direct_op, hipStream_t
 	//    of its probes do (a read that passes all the same costs a resolve pass, never a wrong answer)
 	const uint32_t h = f->hp.h;
 	const uint32_t probes2 = cold_frac <= 0.0025 ? (h + 1) / 2 : cold_frac <= 0.025 ? std::max((h + 1) / 2, h - 1) : h;
-	if ((rc = sample(1, probes2)))
+	if (int rc = sample(1, probes2))
 		return rc;
-	const uint64_t n_warm = n_reads - n_cold;
-	if ((double)n_cold < few_cold) { // the fail list copes with that many misses
-		*decided = 2;
-		return BTLBF_OK;
+	// the fail list copes with that many misses: 2; the warm reads are not worth a sweep of the array: 1; else split
+	*decided = (double)st.n_cold < few_cold ? 2 : warm_too_few((double)(n_reads - st.n_cold)) ? 1 : 3;
+	return BTLBF_OK;
+}
+
+// carve f->split into n buffers of sz[i] bytes (0: none); returns what they take together
+static uint64_t split_carve(const btlbf_filter* f, const uint64_t* sz, uint8_t** q, int n)
+{
+	uint64_t off = 0;
+	for (int i = 0; i < n; ++i) {
+		q[i] = sz[i] ? static_cast<uint8_t*>(f->split.p) + off : nullptr;
+		off += sz[i];
 	}
-	if (warm_too_few((double)n_warm)) { // not worth a sweep of the array
+	return off;
+}
+
+// Uniform reads that pass A takes through its read grid (level-0 plan `pl0`): the warm reads stay where they are -- pass
+// A leaves the cold ones out by their flags (zero-staged: no entries, no bits, no counts) --, only the COLD reads are
+// gathered for the direct kernel, and their answers are ORed back into the caller's bitmaps.  The first version gathered
+// the warm reads as well (15 GB copied and 15 GB of HBM that the partition scratch then lacked: a third batch) and
+// merged every word of the bitmaps from two sources.
+static int split_cold_only(btlbf_filter* f, const SeqArgs& a, int direct_op, hipStream_t s, const SplitState& st,
+                           const PartPlan& pl0, int* decided)
+{
+	const uint32_t L = st.L;
+	const uint64_t n_cold = st.n_cold, cold_len = n_cold * L;
+	const bool wv = a.valid_bits != nullptr;
+	const uint64_t szm[5] = {up256(cold_len + 16), up256(bitmap_bytes(cold_len) + 16), wv ? up256(bitmap_bytes(cold_len) + 16) : 0,
+	                         up256(n_cold * 4 + 16), a.hit_bits ? 0 : up256(bitmap_bytes(a.len) + 16)};
+	uint64_t need = 0;
+	for (uint64_t v : szm)
+		need += v;
+	// (a buffer left behind by a call that gathered the warm reads as well -- 19 GB for 10^8 reads -- is given back
+	// first: the partition scratch is planned from the free HBM, and with that much less of it the pass would need
+	// a third batch, i.e. a third sweep of the array)
+	if (f->split.bytes > 4 * need + (1ull << 30))
+		f->split.release();
+	if (!f->split.grow(need, f->device)) {
 		*decided = 1;
 		return BTLBF_OK;
 	}
-	// ---- split ----
-	const uint64_t warm_len = n_warm * L, cold_len = n_cold * L;
-	const bool wv = a.valid_bits != nullptr;
-	// Uniform reads that pass A takes through its read grid: the warm reads stay where they are -- pass A leaves the
-	// cold ones out by their flags (zero-staged: no entries, no bits, no counts) --, only the COLD reads are gathered for
-	// the direct kernel, and their answers are ORed back into the caller's bitmaps.  The first version gathered the warm
-	// reads as well (15 GB copied and 15 GB of HBM that the partition scratch then lacked: a third batch) and merged
-	// every word of the bitmaps from two sources.
+	uint8_t* q[5];
+	split_carve(f, szm, q, 5);
+	uint8_t *cold_p = q[0], *cold_hit_p = q[1], *cold_valid_p = q[2];
+	uint32_t* cold_index = reinterpret_cast<uint32_t*>(q[3]);
+	uint8_t* hb = a.hit_bits ? a.hit_bits : q[4];
 	{
-		PartPlan pl0;
-		PartGrid g;
-		// (up to a quarter of the reads cold: beyond that the lanes pass A spends on zero-staged reads cost more than
-		// gathering the warm reads costs -- at one read in two 76 instead of 43 ms of pass A per 10^8 reads)
-		if (4 * n_cold <= n_reads && plan_level0(f, pl0, call_probes(f, a.len)) && part_read_grid(f->hp, pl0.lv[0].P, a.layout, &g)) {
-			const uint64_t szm[5] = {up(cold_len + 16), up(bitmap_bytes(cold_len) + 16), wv ? up(bitmap_bytes(cold_len) + 16) : 0,
-			                         up(n_cold * 4 + 16), a.hit_bits ? 0 : up(bitmap_bytes(a.len) + 16)};
-			uint64_t need = 0;
-			for (uint64_t v : szm)
-				need += v;
-			// (a buffer left behind by a call that gathered the warm reads as well -- 19 GB for 10^8 reads -- is given back
-			// first: the partition scratch is planned from the free HBM, and with that much less of it the pass would need
-			// a third batch, i.e. a third sweep of the array)
-			if (f->split_bytes > 4 * need + (1ull << 30)) {
-				(void)hipFree(f->d_split);
-				f->d_split = nullptr;
-				f->split_bytes = 0;
-			}
-			if (!grow(&f->d_split, &f->split_bytes, need)) {
-				*decided = 1;
-				return BTLBF_OK;
-			}
-			uint8_t* q[5];
-			{
-				uint64_t off = 0;
-				for (int i = 0; i < 5; ++i) {
-					q[i] = szm[i] ? static_cast<uint8_t*>(f->d_split) + off : nullptr;
-					off += szm[i];
-				}
-			}
-			uint8_t *cold_p = q[0], *cold_hit_p = q[1], *cold_valid_p = q[2];
-			uint32_t* cold_index = reinterpret_cast<uint32_t*>(q[3]);
-			uint8_t* hb = a.hit_bits ? a.hit_bits : q[4];
-			{
-				ProfSpan ps(f, BTLBF_PROF_QUERY_RESOLVE, s);
-				HIP_TRY(launch_flag_prefix(d_flags, n_reads, d_prefix, s));
-				HIP_TRY(launch_gather_cold_reads(a.seq, n_reads, L, d_flags, d_prefix, cold_p, cold_index, s));
-				HIP_TRY(hipMemsetAsync(cold_hit_p + bitmap_bytes(cold_len), 0, 16, s)); // (the merge reads a word further)
-				if (wv)
-					HIP_TRY(hipMemsetAsync(cold_valid_p + bitmap_bytes(cold_len), 0, 16, s));
-			}
-			SeqArgs b = a;
-			b.read_mask = reinterpret_cast<const uint32_t*>(d_flags);
-			b.hit_bits = b.valid_bits = nullptr;
-			b.counts = nullptr;
-			bool done_w = false;
-			if ((rc = partitioned_contains(f, b, hb, a.valid_bits, a.counts, s, &done_w, true)))
-				return rc;
-			if (!done_w) { // no room for the partition scratch: the gather kernel answers the whole buffer
-				*decided = 1;
-				return BTLBF_OK;
-			}
-			SeqArgs d = a;
-			d.seq = cold_p;
-			d.len = cold_len;
-			d.hit_bits = cold_hit_p;
-			d.valid_bits = cold_valid_p;
-			d.counts = a.counts; // the direct kernel ADDS its clean windows (and its hits: recounted below)
-			{
-				ProfSpan ps(f, BTLBF_PROF_QUERY_DIRECT, s);
-				REQUIRE_MATERIALIZED(f);
-				HIP_TRY(launch_seq_op(direct_op, d, s));
-			}
-			{
-				ProfSpan ps(f, BTLBF_PROF_QUERY_RESOLVE, s);
-				HIP_TRY(launch_merge_cold_bitmaps(n_cold, L, cold_index, reinterpret_cast<const uint64_t*>(cold_hit_p),
-				                                  reinterpret_cast<const uint64_t*>(cold_valid_p), reinterpret_cast<uint64_t*>(hb),
-				                                  reinterpret_cast<uint64_t*>(a.valid_bits), s));
-				if (a.counts) { // hits = set bits of the finished bitmap
-					HIP_TRY(hipMemsetAsync(a.counts + 1, 0, 8, s));
-					HIP_TRY(launch_popcount(hb, bitmap_bytes(a.len), 0, 0, reinterpret_cast<unsigned long long*>(a.counts) + 1, s));
-				}
-			}
-			*decided = 3;
-			return BTLBF_OK;
+		ProfSpan ps(f, BTLBF_PROF_QUERY_RESOLVE, s);
+		HIP_TRY(launch_flag_prefix(st.d_flags, st.n_reads, st.d_prefix, s));
+		HIP_TRY(launch_gather_cold_reads(a.seq, st.n_reads, L, st.d_flags, st.d_prefix, cold_p, cold_index, s));
+		HIP_TRY(hipMemsetAsync(cold_hit_p + bitmap_bytes(cold_len), 0, 16, s)); // (the merge reads a word further)
+		if (wv)
+			HIP_TRY(hipMemsetAsync(cold_valid_p + bitmap_bytes(cold_len), 0, 16, s));
+	}
+	SeqArgs b = a;
+	b.read_mask = reinterpret_cast<const uint32_t*>(st.d_flags);
+	b.hit_bits = b.valid_bits = nullptr;
+	b.counts = nullptr;
+	bool done_w = false;
+	if (int rc = part_query(f, b, hb, a.valid_bits, a.counts, s, &done_w, true, &pl0))
+		return rc;
+	if (!done_w) { // no room for the partition scratch: the gather kernel answers the whole buffer
+		*decided = 1;
+		return BTLBF_OK;
+	}
+	if (int rc = split_direct(f, a, direct_op, cold_p, cold_len, cold_hit_p, cold_valid_p, s)) // (its hits: recounted below)
+		return rc;
+	{
+		ProfSpan ps(f, BTLBF_PROF_QUERY_RESOLVE, s);
+		HIP_TRY(launch_merge_cold_bitmaps(n_cold, L, cold_index, reinterpret_cast<const uint64_t*>(cold_hit_p),
+		                                  reinterpret_cast<const uint64_t*>(cold_valid_p), reinterpret_cast<uint64_t*>(hb),
+		                                  reinterpret_cast<uint64_t*>(a.valid_bits), s));
+		if (a.counts) { // hits = set bits of the finished bitmap
+			HIP_TRY(hipMemsetAsync(a.counts + 1, 0, 8, s));
+			HIP_TRY(launch_popcount(hb, bitmap_bytes(a.len), 0, 0, reinterpret_cast<unsigned long long*>(a.counts) + 1, s));
 		}
 	}
-	const uint64_t sz[6] = {up(warm_len + 16), up(cold_len + 16), up(bitmap_bytes(warm_len) + 16),
-	                        up(bitmap_bytes(cold_len) + 16), wv ? up(bitmap_bytes(warm_len) + 16) : 0,
-	                        wv ? up(bitmap_bytes(cold_len) + 16) : 0};
+	*decided = 3;
+	return BTLBF_OK;
+}
+
+// The reads are compacted into a warm and a cold buffer, the warm one takes the partitioned path (a buffer of its own
+// length, planned for itself), the cold one the early-exit gather kernel, and the two bitmaps are merged back into the
+// caller's layout.
+static int split_warm_cold(btlbf_filter* f, const SeqArgs& a, int direct_op, hipStream_t s, const SplitState& st, int* decided)
+{
+	const uint32_t L = st.L;
+	const uint64_t warm_len = (st.n_reads - st.n_cold) * L, cold_len = st.n_cold * L;
+	const bool wv = a.valid_bits != nullptr;
+	const uint64_t sz[6] = {up256(warm_len + 16), up256(cold_len + 16), up256(bitmap_bytes(warm_len) + 16),
+	                        up256(bitmap_bytes(cold_len) + 16), wv ? up256(bitmap_bytes(warm_len) + 16) : 0,
+	                        wv ? up256(bitmap_bytes(cold_len) + 16) : 0};
 	// sized for any split of a buffer this long, so that the next call's ratio does not move memory
-	const uint64_t worst = up(a.len + 32) + 512 + (wv ? 2 : 1) * (up(bitmap_bytes(a.len) + 32) + 512);
-	if (!grow(&f->d_split, &f->split_bytes, worst)) {
+	const uint64_t worst = up256(a.len + 32) + 512 + (wv ? 2 : 1) * (up256(bitmap_bytes(a.len) + 32) + 512);
+	if (!f->split.grow(worst, f->device)) {
 		*decided = 1; // no room for the compacted copies: the gather kernel answers any mix
 		return BTLBF_OK;
 	}
 	uint8_t* bufs[6];
-	{
-		uint64_t off = 0;
-		for (int i = 0; i < 6; ++i) {
-			bufs[i] = sz[i] ? static_cast<uint8_t*>(f->d_split) + off : nullptr;
-			off += sz[i];
-		}
-		if (off > f->split_bytes)
-			return fail(BTLBF_EINVAL, "split query: buffer arithmetic");
-	}
+	if (split_carve(f, sz, bufs, 6) > f->split.bytes)
+		return fail(BTLBF_EINVAL, "split query: buffer arithmetic");
 	uint8_t *warm_p = bufs[0], *cold_p = bufs[1], *warm_hit_p = bufs[2], *cold_hit_p = bufs[3], *warm_valid_p = bufs[4],
 	        *cold_valid_p = bufs[5];
 	{
 		ProfSpan ps(f, BTLBF_PROF_QUERY_RESOLVE, s);
-		HIP_TRY(launch_flag_prefix(d_flags, n_reads, d_prefix, s));
-		HIP_TRY(launch_compact_reads(a.seq, n_reads, L, d_flags, d_prefix, warm_p, cold_p, s));
+		HIP_TRY(launch_flag_prefix(st.d_flags, st.n_reads, st.d_prefix, s));
+		HIP_TRY(launch_compact_reads(a.seq, st.n_reads, L, st.d_flags, st.d_prefix, warm_p, cold_p, s));
 		// the merge reads one word past the last bit of a compacted bitmap
 		HIP_TRY(hipMemsetAsync(warm_hit_p + bitmap_bytes(warm_len), 0, 16, s));
 		HIP_TRY(hipMemsetAsync(cold_hit_p + bitmap_bytes(cold_len), 0, 16, s));
@@ -993,35 +1005,41 @@ int split_contains(btlbf_filter* f, const SeqArgs& a, int direct_op, hipStream_t
 	b.hit_bits = b.valid_bits = nullptr;
 	b.counts = nullptr;
 	bool done_w = false;
-	rc = partitioned_contains(f, b, warm_hit_p, warm_valid_p, a.counts, s, &done_w);
-	if (rc)
+	if (int rc = part_query(f, b, warm_hit_p, warm_valid_p, a.counts, s, &done_w, false, nullptr))
 		return rc;
-	if (!done_w) { // no room for the partition scratch: the gather kernel does the warm reads too
-		b.hit_bits = warm_hit_p;
-		b.valid_bits = warm_valid_p;
-		b.counts = a.counts;
-		ProfSpan ps(f, BTLBF_PROF_QUERY_DIRECT, s);
-		HIP_TRY(launch_seq_op(direct_op, b, s));
-	}
-	SeqArgs d = a;
-	d.seq = cold_p;
-	d.len = cold_len;
-	d.hit_bits = cold_hit_p;
-	d.valid_bits = cold_valid_p;
-	d.counts = a.counts; // the direct kernel ADDS its clean windows and hits
-	{
-		ProfSpan ps(f, BTLBF_PROF_QUERY_DIRECT, s);
-		HIP_TRY(launch_seq_op(direct_op, d, s));
-	}
+	int rc = BTLBF_OK;
+	if (!done_w) // no room for the partition scratch: the gather kernel does the warm reads too
+		rc = split_direct(f, a, direct_op, warm_p, warm_len, warm_hit_p, warm_valid_p, s);
+	if (rc || (rc = split_direct(f, a, direct_op, cold_p, cold_len, cold_hit_p, cold_valid_p, s)))
+		return rc;
 	if (a.hit_bits || a.valid_bits) {
 		ProfSpan ps(f, BTLBF_PROF_QUERY_RESOLVE, s);
-		HIP_TRY(launch_merge_split_bitmaps(a.len, L, d_flags, d_prefix, reinterpret_cast<uint64_t*>(warm_hit_p),
+		HIP_TRY(launch_merge_split_bitmaps(a.len, L, st.d_flags, st.d_prefix, reinterpret_cast<uint64_t*>(warm_hit_p),
 		                                   reinterpret_cast<uint64_t*>(cold_hit_p), reinterpret_cast<uint64_t*>(warm_valid_p),
 		                                   reinterpret_cast<uint64_t*>(cold_valid_p), reinterpret_cast<uint64_t*>(a.hit_bits),
 		                                   reinterpret_cast<uint64_t*>(a.valid_bits), s));
 	}
 	*decided = 3;
 	return BTLBF_OK;
+}
+
+// Sample every read (split_decide); if the misses are few enough for the fail list the whole buffer goes partitioned
+// (*decided = 2), if hardly anything hits it goes to the gather kernel (1); otherwise the warm reads take the partitioned
+// path and the cold ones the gather kernel, by one of the two executors above (3: a.hit_bits / a.valid_bits / a.counts
+// are complete).
+int split_contains(btlbf_filter* f, const SeqArgs& a, int direct_op, hipStream_t s, int* decided)
+{
+	SplitState st;
+	int rc = split_decide(f, a, s, st, decided);
+	if (rc || *decided != 3)
+		return rc;
+	// (up to a quarter of the reads cold: beyond that the lanes pass A spends on zero-staged reads cost more than
+	// gathering the warm reads costs -- at one read in two 76 instead of 43 ms of pass A per 10^8 reads)
+	PartPlan pl0; // level 0 is planned here, once: the partitioned query takes it over (the grid belongs to its geometry)
+	PartGrid g;
+	if (4 * st.n_cold <= st.n_reads && plan_level0(f, pl0, call_probes(f, a.len)) && part_read_grid(f->hp, pl0.lv[0].P, a.layout, &g))
+		return split_cold_only(f, a, direct_op, s, st, pl0, decided);
+	return split_warm_cold(f, a, direct_op, s, st, decided);
 }
 
 } // namespace btlbf
@@ -1032,15 +1050,8 @@ extern "C" int btlbf_route_plan(btlbf_filter* f, uint64_t len, const btlbf_layou
 	FilterLock lk__(f);
 	if (!f || !ent_bytes_per_shard || !cnt_bytes_per_shard)
 		return fail(BTLBF_EINVAL, "null argument");
-	LayoutParams lay{nullptr, 0, 0};
-	if (layout) {
-		lay.starts = layout->starts;
-		lay.n_seqs = layout->n_seqs;
-		lay.read_len = layout->starts ? 0 : layout->read_len;
-	}
 	RoutePlan rp;
-	int rc = route_plan(f, len, lay, n_shards, rp);
-	if (rc)
+	if (int rc = plan_routed(f, len, layout_params(layout), n_shards, 0, false, rp))
 		return rc;
 	*ent_bytes_per_shard = rp.ent_bytes_per_shard;
 	*cnt_bytes_per_shard = rp.cnt_bytes_per_shard;
@@ -1071,8 +1082,7 @@ extern "C" int btlbf_route_windows(btlbf_filter* f, unsigned n_shards, unsigned*
 	if (!f || !n_windows || !shards_per_window)
 		return fail(BTLBF_EINVAL, "null argument");
 	RoutePlan rp;
-	int rc = route_plan(f, 1, LayoutParams{nullptr, 0, 0}, n_shards, rp);
-	if (rc)
+	if (int rc = plan_routed(f, 1, layout_params(nullptr), n_shards, 0, false, rp))
 		return rc;
 	*n_windows = rp.n_windows;
 	*shards_per_window = rp.shards_per_window;
@@ -1085,7 +1095,7 @@ extern "C" int btlbf_route_seqs(btlbf_filter* f, const char* seq, uint64_t len, 
                                 uint64_t* spill_list, uint64_t spill_cap, uint64_t* spill_count, void* stream)
 {
 	FilterLock lk__(f);
-	int rc = seq_precheck(f, len);
+	int rc = seq_precheck(f);
 	if (rc)
 		return rc;
 	if (!send_ent || !send_cnt || !spill_list || !spill_count)
@@ -1096,7 +1106,7 @@ extern "C" int btlbf_route_seqs(btlbf_filter* f, const char* seq, uint64_t len, 
 	if ((rc = make_view(v, seq, len, layout, BTLBF_DEVICE, s)))
 		return rc;
 	RoutePlan rp;
-	if ((rc = route_plan(f, plan_len, v.lay, n_shards, rp)))
+	if ((rc = plan_routed(f, plan_len, v.lay, n_shards, 0, false, rp)))
 		return rc;
 	if (window >= rp.n_windows)
 		return fail(BTLBF_EINVAL, "window %u of %u", window, rp.n_windows);
@@ -1109,12 +1119,11 @@ extern "C" int btlbf_route_seqs(btlbf_filter* f, const char* seq, uint64_t len, 
 	a.first_tile = 0;
 	a.n_tiles = part_tiling(f->hp, rp.bins, v.lay, len).n_tiles;
 	PartOut out{rp.bins, rp.regions, rp.cap, static_cast<uint32_t*>(send_cnt), static_cast<uint32_t*>(send_ent)};
-	PartSide sd;
-	memset(&sd, 0, sizeof sd);
+	PartSide sd = part_side(f); // (pass A leaves the array alone: whatever misses its rings is spilled)
 	sd.spill_list = spill_list;
 	sd.spill_count = reinterpret_cast<unsigned long long*>(spill_count);
 	sd.spill_cap = spill_cap;
-	sd.pos_base = a.mod.shard_lo; // spilled entries travel as global positions
+	sd.pos_base = a.mod.shard_lo; // spilled entries travel as global positions, and their bins are this window's
 	// spill_count and counts ACCUMULATE over the batches of a pass (the caller zeroes them once): no
 	// host round trip per batch, so the exchange of one batch can overlap the hashing of the next
 	if (a.n_tiles == 0) { // nothing to hash: still publish empty regions
@@ -1132,18 +1141,13 @@ extern "C" int btlbf_route_geometry(btlbf_filter* f, uint64_t plan_len, const bt
 	FilterLock lk__(f);
 	if (!f || !out4)
 		return fail(BTLBF_EINVAL, "null argument");
-	const LayoutParams lay = layout_params(layout);
 	RoutePlan rp;
-	int rc = route_plan(f, plan_len, lay, n_shards, rp);
-	if (rc)
-		return rc;
-	PartPlan pl;
-	if ((rc = owner_plan(f, rp, lay, plan_len, n_blocks ? n_blocks : n_shards, n_shards, pl)))
+	if (int rc = plan_routed(f, plan_len, layout_params(layout), n_shards, n_blocks, true, rp))
 		return rc;
 	out4[0] = rp.bins_per_shard;
 	out4[1] = rp.regions;
 	out4[2] = rp.cap;
-	out4[3] = pl.n_levels >= 2 && pl.group_bins ? pl.group_bins : rp.bins_per_shard;
+	out4[3] = rp.owner.group(rp.bins_per_shard);
 	return BTLBF_OK;
 }
 
@@ -1153,15 +1157,10 @@ extern "C" int btlbf_owner_scratch_bytes(btlbf_filter* f, uint64_t plan_len, con
 	FilterLock lk__(f);
 	if (!f || !bytes)
 		return fail(BTLBF_EINVAL, "null argument");
-	const LayoutParams lay = layout_params(layout);
 	RoutePlan rp;
-	int rc = route_plan(f, plan_len, lay, n_shards, rp);
-	if (rc)
+	if (int rc = plan_routed(f, plan_len, layout_params(layout), n_shards, n_blocks, true, rp))
 		return rc;
-	PartPlan pl;
-	if ((rc = owner_plan(f, rp, lay, plan_len, n_blocks ? n_blocks : n_shards, n_shards, pl)))
-		return rc;
-	*bytes = pl.bytes_total;
+	*bytes = rp.owner.bytes_total;
 	return BTLBF_OK;
 }
 
@@ -1171,44 +1170,11 @@ extern "C" int btlbf_apply_routed_bins(btlbf_filter* f, const void* recv_ent, co
                                        uint64_t fail_cap, uint64_t* fail_count, void* stream)
 {
 	FilterLock lk__(f);
-	if (!f || !recv_ent || !recv_cnt || n_blocks == 0)
-		return fail(BTLBF_EINVAL, "null argument");
-	if (f->shard_count != n_shards)
-		return fail(BTLBF_EINVAL, "filter is shard %u of %u, not of %u", f->shard_index, f->shard_count, n_shards);
-	if (query && (!fail_list || !fail_count))
-		return fail(BTLBF_EINVAL, "query needs a fail list");
-	DeviceGuard g(f->device);
-	hipStream_t s = static_cast<hipStream_t>(stream);
-	MATERIALIZE(f, s);
-	const LayoutParams lay = layout_params(layout);
 	RoutePlan rp;
-	int rc = route_plan(f, plan_len, lay, n_shards, rp);
-	if (rc)
+	if (int rc = plan_routed(f, plan_len, layout_params(layout), n_shards, n_blocks, true, rp))
 		return rc;
-	PartPlan pl;
-	if ((rc = owner_plan(f, rp, lay, plan_len, n_blocks, n_shards, pl)))
-		return rc;
-	const uint32_t group = pl.n_levels >= 2 && pl.group_bins ? pl.group_bins : rp.bins_per_shard;
-	if (n_bins == 0 || first_bin + n_bins > rp.bins_per_shard || first_bin % group || (n_bins % group && first_bin + n_bins != rp.bins_per_shard))
-		return fail(BTLBF_EINVAL, "bins [%u, +%u) are not whole groups of %u of this shard's %u level-0 bins", first_bin,
-		            n_bins, group, rp.bins_per_shard);
-	bool ok = false;
-	if ((rc = ensure_scratch(f, pl.bytes_total, &ok)))
-		return rc;
-	if (!ok)
-		return fail(BTLBF_ENOMEM, "no room for %llu bytes of partition scratch", (unsigned long long)pl.bytes_total);
-	carve_levels(pl, static_cast<uint8_t*>(f->d_part), 1);
-	PartSide sd;
-	memset(&sd, 0, sizeof sd);
-	sd.pos_base = f->mod.shard_lo;
-	sd.fail_list = fail_list;
-	sd.fail_count = reinterpret_cast<unsigned long long*>(fail_count);
-	sd.fail_cap = fail_cap;
-	sd.counting = f->kind == BTLBF_COUNTING8; // incrementAll / counter >= threshold at the owner
-	sd.threshold = f->thr;
-	PartIn in0{n_blocks, n_bins, rp.regions, rp.cap, static_cast<const uint32_t*>(recv_cnt),
-	           static_cast<const uint32_t*>(recv_ent)};
-	return run_levels(f, pl, in0, sd, query, s, first_bin, n_bins);
+	return apply_routed(f, rp, recv_ent, recv_cnt, n_blocks, first_bin, n_bins, n_shards, query, fail_list, fail_cap,
+	                    fail_count, stream);
 }
 
 extern "C" int btlbf_apply_routed(btlbf_filter* f, const void* recv_ent, const void* recv_cnt, unsigned n_blocks,
@@ -1216,15 +1182,11 @@ extern "C" int btlbf_apply_routed(btlbf_filter* f, const void* recv_ent, const v
                                   uint64_t* fail_list, uint64_t fail_cap, uint64_t* fail_count, void* stream)
 {
 	FilterLock lk__(f);
-	if (!f)
-		return fail(BTLBF_EINVAL, "null argument");
-	const LayoutParams lay = layout_params(layout);
 	RoutePlan rp;
-	int rc = route_plan(f, plan_len, lay, n_shards, rp);
-	if (rc)
+	if (int rc = plan_routed(f, plan_len, layout_params(layout), n_shards, n_blocks, true, rp))
 		return rc;
-	return btlbf_apply_routed_bins(f, recv_ent, recv_cnt, n_blocks, 0, rp.bins_per_shard, plan_len, layout, n_shards,
-	                               query, fail_list, fail_cap, fail_count, stream);
+	return apply_routed(f, rp, recv_ent, recv_cnt, n_blocks, 0, rp.bins_per_shard, n_shards, query, fail_list,
+	                    fail_cap, fail_count, stream);
 }
 
 extern "C" int btlbf_apply_spill(btlbf_filter* f, const uint64_t* global_pos, uint64_t n, int query,
@@ -1235,13 +1197,10 @@ extern "C" int btlbf_apply_spill(btlbf_filter* f, const uint64_t* global_pos, ui
 		return fail(BTLBF_EINVAL, "null argument");
 	DeviceGuard g(f->device);
 	MATERIALIZE(f, stream);
-	PartSide sd;
-	memset(&sd, 0, sizeof sd);
+	PartSide sd = part_side(f);
 	sd.fail_list = fail_list;
 	sd.fail_count = reinterpret_cast<unsigned long long*>(fail_count);
 	sd.fail_cap = fail_cap;
-	sd.counting = f->kind == BTLBF_COUNTING8;
-	sd.threshold = f->thr;
 	HIP_TRY(launch_spill(f->d_data, global_pos, n, f->mod.shard_lo, f->mod.shard_len, query, sd,
 	                     static_cast<hipStream_t>(stream)));
 	return BTLBF_OK;
@@ -1251,7 +1210,7 @@ extern "C" int btlbf_resolve_seqs(btlbf_filter* f, const char* seq, uint64_t len
                                   const uint64_t* fail_list, uint64_t n_fail, uint64_t* hit_bits, void* stream)
 {
 	FilterLock lk__(f);
-	int rc = seq_precheck(f, len);
+	int rc = seq_precheck(f);
 	if (rc)
 		return rc;
 	if (!hit_bits || (n_fail && !fail_list))
@@ -1265,13 +1224,21 @@ extern "C" int btlbf_resolve_seqs(btlbf_filter* f, const char* seq, uint64_t len
 	SeqView v;
 	if ((rc = make_view(v, seq, len, layout, BTLBF_DEVICE, s)))
 		return rc;
-	bool ok = false;
-	if ((rc = ensure_scratch(f, kFailTableSlots * 8, &ok)))
-		return rc;
-	if (!ok)
+	if (!f->part.grow(kFailTableSlots * 8, f->device))
 		return fail(BTLBF_ENOMEM, "no room for the failed-position set");
 	SeqArgs a = base_args(f, v, len);
 	fill_mod(a.mod, f->mod.size, 0, f->mod.size); // global positions
-	return resolve_range(f, a, reinterpret_cast<uint8_t*>(hit_bits), fail_list, n_fail,
-	                     static_cast<uint64_t*>(f->d_part), kFailTableSlots, 0, 0, s);
+	a.hit_bits = reinterpret_cast<uint8_t*>(hit_bits);
+	// the table is sized to the set (load <= 1/4): a few thousand failed positions make a table that stays in
+	// L2, and every probe of every window is looked up in it
+	uint64_t* table = static_cast<uint64_t*>(f->part.p);
+	uint64_t slots = 1024;
+	while (slots < 4 * n_fail && slots < kFailTableSlots)
+		slots <<= 1;
+	HIP_TRY(hipMemsetAsync(table, 0, slots * 8, s));
+	HIP_TRY(launch_failset_build(fail_list, n_fail, table, slots - 1, s));
+	a.buckets = table;
+	a.bucket_cap = slots - 1;
+	HIP_TRY(launch_seq_op(OP_BF_RESOLVE, a, s));
+	return BTLBF_OK;
 }

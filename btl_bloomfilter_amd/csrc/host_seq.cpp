@@ -17,13 +17,12 @@ using namespace btlbf;
 // -------------------------------------------------------------------------------------------------
 namespace btlbf {
 
-int seq_precheck(const btlbf_filter* f, uint64_t len)
+int seq_precheck(const btlbf_filter* f)
 {
 	if (!f)
 		return fail(BTLBF_EINVAL, "null filter");
 	if (f->hp.n_seeds == 0 && f->h > 64)
 		return fail(BTLBF_EINVAL, "hash_num %u > 64 unsupported by the sequence kernels", f->h);
-	(void)len;
 	return BTLBF_OK;
 }
 
@@ -35,7 +34,7 @@ int run_query_like(btlbf_filter* f, int op, const char* seq, uint64_t len, const
                    uint64_t* hit_bits, uint64_t* valid_bits, uint64_t* counts, uint8_t* min_out, int mem,
                    void* stream, FilterLock* lk = nullptr)
 {
-	int rc = seq_precheck(f, len);
+	int rc = seq_precheck(f);
 	if (rc)
 		return rc;
 	// contains() on a shard answers for the probes inside its window (ShardedBloomFilter's gather mode
@@ -253,7 +252,7 @@ extern "C" int btlbf_insert_seqs(btlbf_filter* f, const char* seq, uint64_t len,
                                  const btlbf_layout* layout, int op, int order, int mem, void* stream)
 {
 	FilterLock lk__(f);
-	int rc = seq_precheck(f, len);
+	int rc = seq_precheck(f);
 	if (rc)
 		return rc;
 	DeviceGuard g(f->device);
