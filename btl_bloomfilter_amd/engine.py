@@ -79,11 +79,54 @@ def bits_to_bool(bits, n):
     return np.unpackbits(b, bitorder="little")[:n].astype(bool)
 
 
-def _bitmap(n):
-    return np.zeros((n + 63) // 64, np.uint64)
+def _words(n):
+    return (n + 63) // 64
 
 
-class _Filter:
+def _out(b, shape, dtype):
+    """A zeroed output in the memory space of the input _Buf `b` -> (output, its c_void_p); (None, None) for an
+    optional output that was not asked for (shape None).  Device input: a torch tensor on the input's device, of
+    torch's same-width signed type where torch has no unsigned one (bitmaps and hashes are int64).  Host input: a
+    numpy array of at least one element along its first axis, sliced back to the shape asked for."""
+    if shape is None:
+        return None, None
+    shape = shape if isinstance(shape, tuple) else (int(shape),)
+    if b.mem == DEVICE:
+        import torch
+
+        name = np.dtype(dtype).name
+        t = torch.zeros(shape, dtype=getattr(torch, name if name == "uint8" else name.lstrip("u")),
+                        device=b.keep.device)
+        return t, C.c_void_p(t.data_ptr())
+    a = np.zeros((max(shape[0], 1),) + shape[1:], dtype)
+    return a[: shape[0]], C.c_void_p(a.ctypes.data)
+
+
+_MODES = {"auto": 0, "direct": 1, "partitioned": 2}
+
+
+def _mode(mode):
+    return _MODES[mode] if isinstance(mode, str) else int(mode)
+
+
+class _Owned:
+    """a library handle in self._h that the call named by `_destroy` releases"""
+
+    _destroy = "btlbf_destroy"
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(self._L, self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _Filter(_Owned):
     kind = BLOOM
 
     def __init__(self, handle):
@@ -105,17 +148,6 @@ class _Filter:
         h = C.c_void_p()
         check(L.btlbf_load(C.byref(h), cls.kind, str(path).encode(), int(threshold), int(device)))
         return h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.btlbf_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # -- attributes (reference getters) ------------------------------------------------------
     def getHashNum(self):
@@ -172,8 +204,7 @@ class _Filter:
 
     def setInsertMode(self, mode, scratch_bytes=0):
         """'auto' | 'direct' | 'partitioned' (see btlbf_set_insert_mode)"""
-        m = {"auto": 0, "direct": 1, "partitioned": 2}[mode] if isinstance(mode, str) else int(mode)
-        check(self._L.btlbf_set_insert_mode(self._h, m, int(scratch_bytes)))
+        check(self._L.btlbf_set_insert_mode(self._h, _mode(mode), int(scratch_bytes)))
 
     def releaseScratch(self):
         check(self._L.btlbf_release_scratch(self._h))
@@ -190,8 +221,7 @@ class _Filter:
 
     def setQueryMode(self, mode):
         """'auto' | 'direct' | 'partitioned' (see btlbf_set_query_mode)"""
-        m = {"auto": 0, "direct": 1, "partitioned": 2}[mode] if isinstance(mode, str) else int(mode)
-        check(self._L.btlbf_set_query_mode(self._h, m))
+        check(self._L.btlbf_set_query_mode(self._h, _mode(mode)))
 
     # -- FASTA / FASTQ files (btlbf_insert_fastx / btlbf_contains_fastx) -----------------------------
     def insertFile(self, path, per_line=False, batch_bytes=0):
@@ -219,19 +249,10 @@ class _Filter:
         b = _Buf(seq)
         lay, keep = _layout(starts, read_len, b.mem)
         n = b.nbytes
-        if b.mem == DEVICE:
-            import torch
-
-            hit = torch.zeros((n + 63) // 64, dtype=torch.int64, device=b.keep.device)
-            valid = torch.zeros_like(hit) if want_valid else None
-            cnt = torch.zeros(2, dtype=torch.int64, device=b.keep.device) if want_counts else None
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-        else:
-            hit = _bitmap(n)
-            valid = _bitmap(n) if want_valid else None
-            cnt = np.zeros(2, np.uint64) if want_counts else None
-            ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None  # noqa: E731
-        check(fn(self._h, b.ptr, n, C.byref(lay) if lay else None, ptr(hit), ptr(valid), ptr(cnt), b.mem,
+        hit, p_hit = _out(b, _words(n), np.uint64)
+        valid, p_valid = _out(b, _words(n) if want_valid else None, np.uint64)
+        cnt, p_cnt = _out(b, 2 if want_counts else None, np.uint64)
+        check(fn(self._h, b.ptr, n, C.byref(lay) if lay else None, p_hit, p_valid, p_cnt, b.mem,
                  _stream_ptr(stream, b.keep)))
         return hit, valid, cnt
 
@@ -256,16 +277,9 @@ class _Filter:
 
     def _rows_out(self, fn, hashes, *extra, stream=None):
         b, n = self._rows(hashes)
-        if b.mem == DEVICE:
-            import torch
-
-            out = torch.zeros(n, dtype=torch.uint8, device=b.keep.device)
-            optr = C.c_void_p(out.data_ptr())
-        else:
-            out = np.zeros(max(n, 1), np.uint8)
-            optr = C.c_void_p(out.ctypes.data)
+        out, optr = _out(b, n, np.uint8)
         check(fn(self._h, b.ptr, n, optr, *extra, b.mem, _stream_ptr(stream, b.keep)))
-        return out[:n]
+        return out
 
 
 class BloomFilter(_Filter):
@@ -363,30 +377,25 @@ class KmerBloomFilter(BloomFilter):
             out += b[:k]
         return np.frombuffer(bytes(out), np.uint8), len(items)
 
+    def _kmer_buf(self, kmers):
+        """strings, or a uint8 buffer of n*k bytes (numpy / torch on the GPU) -> (_Buf, n)"""
+        if isinstance(kmers, np.ndarray) or _is_torch_cuda(kmers):
+            b = _Buf(kmers)
+            return b, b.nbytes // self.getKmerSize()
+        buf, n = self._kmers(kmers)
+        return _Buf(buf), n
+
     def insertKmers(self, kmers, stream=None):
         """KmerBloomFilter::insert(const char*) for a batch of raw k-mers (strings, or a uint8 buffer of n*k)"""
-        buf, n = self._kmers(kmers) if not isinstance(kmers, np.ndarray) and not _is_torch_cuda(kmers) else (
-            kmers, None)
-        b = _Buf(buf)
-        n = b.nbytes // self.getKmerSize() if n is None else n
+        b, n = self._kmer_buf(kmers)
         check(self._L.btlbf_insert_kmers(self._h, b.ptr, n, 0, ORDER_PARALLEL, b.mem, _stream_ptr(stream, b.keep)))
 
     def containsKmers(self, kmers, stream=None):
         """KmerBloomFilter::contains(const char*) for a batch of raw k-mers -> uint8 array"""
-        buf, n = self._kmers(kmers) if not isinstance(kmers, np.ndarray) and not _is_torch_cuda(kmers) else (
-            kmers, None)
-        b = _Buf(buf)
-        n = b.nbytes // self.getKmerSize() if n is None else n
-        if b.mem == DEVICE:
-            import torch
-
-            out = torch.zeros(n, dtype=torch.uint8, device=b.keep.device)
-            optr = C.c_void_p(out.data_ptr())
-        else:
-            out = np.zeros(max(n, 1), np.uint8)
-            optr = C.c_void_p(out.ctypes.data)
+        b, n = self._kmer_buf(kmers)
+        out, optr = _out(b, n, np.uint8)
         check(self._L.btlbf_contains_kmers(self._h, b.ptr, n, optr, b.mem, _stream_ptr(stream, b.keep)))
-        return out[:n]
+        return out
 
     def insert(self, x, stream=None):
         if self._is_kmer(x):
@@ -510,41 +519,24 @@ class CountingBloomFilter(_Filter):
         b = _Buf(seq)
         lay, keep = _layout(starts, read_len, b.mem)
         n = b.nbytes
-        if b.mem == DEVICE:
-            import torch
-
-            mn = torch.zeros(n, dtype=torch.uint8, device=b.keep.device)
-            valid = torch.zeros((n + 63) // 64, dtype=torch.int64, device=b.keep.device)
-            p1, p2 = C.c_void_p(mn.data_ptr()), C.c_void_p(valid.data_ptr())
-        else:
-            mn = np.zeros(max(n, 1), np.uint8)
-            valid = _bitmap(n)
-            p1, p2 = C.c_void_p(mn.ctypes.data), C.c_void_p(valid.ctypes.data)
+        mn, p1 = _out(b, n, np.uint8)
+        valid, p2 = _out(b, _words(n), np.uint64)
         check(self._L.btlbf_min_count_seqs(self._h, b.ptr, n, C.byref(lay) if lay else None, p1, p2, b.mem,
                                            _stream_ptr(stream, b.keep)))
-        return mn[:n], valid
+        return mn, valid
 
 
-class RankSupport:
+class RankSupport(_Owned):
     """sdsl::bit_vector_il<512> + rank_support_il<1> over a bit filter, in HBM (btlbf_rank_*): what the
     reference's miBF uses to turn a set bit into an index of its ID array (MIBloomFilter.hpp:527,801-803)"""
+
+    _destroy = "btlbf_rank_destroy"
 
     def __init__(self, bloom):
         self._L = _lib.load()
         h = C.c_void_p()
         check(self._L.btlbf_rank_create(C.byref(h), bloom._h))
         self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.btlbf_rank_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def ones(self):
         return self._L.btlbf_rank_ones(self._h)
@@ -575,21 +567,12 @@ def _hash_seqs(seq, k, h, seeds, h2, starts, read_len, device, stream):
     if seeds is not None:
         ns = len(seeds)
         sarr = (C.c_char_p * ns)(*[s.encode() if isinstance(s, str) else s for s in seeds])
-    if b.mem == DEVICE:
-        import torch
-
-        hv = torch.zeros((n, h), dtype=torch.int64, device=b.keep.device)
-        valid = torch.zeros((n + 63) // 64, dtype=torch.int64, device=b.keep.device)
-        st = torch.zeros(n, dtype=torch.int64, device=b.keep.device) if seeds is not None else None
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-    else:
-        hv = np.zeros((max(n, 1), h), np.uint64)
-        valid = _bitmap(n)
-        st = np.zeros(max(n, 1), np.uint64) if seeds is not None else None
-        ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None  # noqa: E731
-    check(L.btlbf_hash_seqs(k, h, sarr, ns, h2, b.ptr, n, C.byref(lay) if lay else None, ptr(hv), ptr(valid),
-                            ptr(st), b.mem, device, _stream_ptr(stream, b.keep)))
-    return hv[:n], valid, (st[:n] if st is not None else None)
+    hv, p_hv = _out(b, (n, h), np.uint64)
+    valid, p_valid = _out(b, _words(n), np.uint64)
+    st, p_st = _out(b, n if seeds is not None else None, np.uint64)
+    check(L.btlbf_hash_seqs(k, h, sarr, ns, h2, b.ptr, n, C.byref(lay) if lay else None, p_hv, p_valid, p_st, b.mem,
+                            device, _stream_ptr(stream, b.keep)))
+    return hv, valid, st
 
 
 def hash_seqs(seq, h, k, starts=None, read_len=0, device=0, stream=None):
@@ -624,15 +607,8 @@ def count_per_seq(hit_bits, valid_bits, n_bytes, k, starts=None, read_len=0, dev
         raise ValueError("count_per_seq needs starts or read_len")
     n_seqs = lay.n_seqs if starts is not None else n_bytes // read_len
     vb = _Buf(valid_bits, np.uint64) if valid_bits is not None else None
-    if hb.mem == DEVICE:
-        import torch
-
-        hits = torch.zeros(n_seqs, dtype=torch.int32, device=hb.keep.device)
-        valid = torch.zeros(n_seqs, dtype=torch.int32, device=hb.keep.device)
-        p1, p2 = C.c_void_p(hits.data_ptr()), C.c_void_p(valid.data_ptr())
-    else:
-        hits, valid = np.zeros(n_seqs, np.uint32), np.zeros(n_seqs, np.uint32)
-        p1, p2 = C.c_void_p(hits.ctypes.data), C.c_void_p(valid.ctypes.data)
+    hits, p1 = _out(hb, n_seqs, np.uint32)
+    valid, p2 = _out(hb, n_seqs, np.uint32)
     check(_lib.load().btlbf_count_per_seq(hb.ptr, vb.ptr if vb is not None else None, int(n_bytes), C.byref(lay), int(k),
                                            p1, p2, hb.mem, device, _stream_ptr(stream, hb.keep)))
     return hits, valid
@@ -666,10 +642,12 @@ def fastx_batches(path, k, per_line=False, batch_bytes=0, pageable=True, byte_ra
         L.btlbf_fastx_close(r)
 
 
-class MIBloomFilter:
+class MIBloomFilter(_Owned):
     """Multi-index Bloom filter over a stage-1 bit filter (btlbf_mibf_*; MIBloomFilter.hpp, MIBFConstructSupport.hpp,
     MIBFQuerySupport.hpp): an ID array of uint16 (id_bytes=2) or uint32 (id_bytes=4) in HBM, addressed by
     rank(hash % size).  The stage-1 filter may be closed once this object exists."""
+
+    _destroy = "btlbf_mibf_destroy"
 
     def __init__(self, stage1_filter, id_bytes=2, _handle=None):
         self._L = _lib.load()
@@ -689,17 +667,6 @@ class MIBloomFilter:
         h = C.c_void_p()
         check(L.btlbf_mibf_load(C.byref(h), str(path).encode(), bloom._h, int(id_bytes)))
         return cls(None, id_bytes, _handle=h)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.btlbf_mibf_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def getPop(self):
         return self._L.btlbf_mibf_size(self._h)
@@ -738,19 +705,12 @@ class MIBloomFilter:
     def insertSaturation(self, seqs, ids, starts=None, read_len=0, serial=False, stream=None):
         """insertSaturation (MIBFConstructSupport.hpp:132-214) -> {clean, found, mutated, saturated}"""
         b, lay, keep, ib = self._seq_args(seqs, ids, starts, read_len)
-        out = np.zeros(4, np.uint64)
-        if b.mem == DEVICE:
-            import torch
-
-            t = torch.zeros(4, dtype=torch.int64, device=b.keep.device)
-            optr = C.c_void_p(t.data_ptr())
-        else:
-            optr = C.c_void_p(out.ctypes.data)
+        out, optr = _out(b, 4, np.uint64)
         check(self._L.btlbf_mibf_saturate_seqs(self._h, b.ptr, b.nbytes, C.byref(lay) if lay else None, ib.ptr,
                                                ORDER_SERIAL if serial else ORDER_PARALLEL, optr, b.mem,
                                                _stream_ptr(stream, b.keep)))
         if b.mem == DEVICE:
-            out = t.cpu().numpy().astype(np.uint64)
+            out = out.cpu().numpy().astype(np.uint64)
         return dict(zip(("clean", "found", "mutated", "saturated"), (int(x) for x in out)))
 
     def query(self, seqs, max_miss=0, starts=None, read_len=0, want_counts=False, stream=None):
@@ -758,23 +718,12 @@ class MIBloomFilter:
         (+ counts {clean, matched} with want_counts); decode(values) gives (id, saturated)"""
         b, lay, keep, _ = self._seq_args(seqs, None, starts, read_len)
         n, h = b.nbytes, self.getHashNum()
-        if b.mem == DEVICE:
-            import torch
-
-            tdt = torch.int16 if self.id_bytes == 2 else torch.int32
-            vals = torch.zeros((n, h), dtype=tdt, device=b.keep.device)
-            hit = torch.zeros((n + 63) // 64, dtype=torch.int64, device=b.keep.device)
-            valid = torch.zeros_like(hit)
-            cnt = torch.zeros(2, dtype=torch.int64, device=b.keep.device)
-            ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        else:
-            vals = np.zeros((max(n, 1), h), self.dtype)
-            hit, valid, cnt = _bitmap(n), _bitmap(n), np.zeros(2, np.uint64)
-            ptr = lambda a: C.c_void_p(a.ctypes.data)  # noqa: E731
-        check(self._L.btlbf_mibf_query_seqs(self._h, b.ptr, n, C.byref(lay) if lay else None, int(max_miss), ptr(vals),
-                                            ptr(hit), ptr(valid), ptr(cnt), b.mem, _stream_ptr(stream, b.keep)))
-        if b.mem != DEVICE:
-            vals = vals[:n]
+        vals, p_vals = _out(b, (n, h), self.dtype)
+        hit, p_hit = _out(b, _words(n), np.uint64)
+        valid, p_valid = _out(b, _words(n), np.uint64)
+        cnt, p_cnt = _out(b, 2, np.uint64)
+        check(self._L.btlbf_mibf_query_seqs(self._h, b.ptr, n, C.byref(lay) if lay else None, int(max_miss), p_vals,
+                                            p_hit, p_valid, p_cnt, b.mem, _stream_ptr(stream, b.keep)))
         return (vals, hit, valid, cnt) if want_counts else (vals, hit, valid)
 
     def decode(self, values):
