@@ -13,10 +13,12 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 ORACLE_SO = os.path.join(_HERE, "libbtl_oracle.so")
-REF_SO = os.path.join(_HERE, "_ref", "libbtlref.so")
+# BTLBF_REF_SO: another build of the same driver (tools/sanitize_host.sh loads the instrumented one)
+REF_SO = os.environ.get("BTLBF_REF_SO") or os.path.join(_HERE, "_ref", "libbtlref.so")
 
 u64p = np.ctypeslib.ndpointer(np.uint64, flags="C_CONTIGUOUS")
 u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
+u32p = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
 
 
 def build(verbose=False):
@@ -287,6 +289,31 @@ class Ref:
         L.ref_bf_spaced_synth.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint, C.c_uint, C.c_uint64, C.c_uint64,
                                           C.c_uint64, C.c_uint, C.c_int]
 
+        if self.has_mibf():  # a _ref built before oracle/ref_mibf_driver.cpp existed has none of these
+            L.ref_mibf_new.restype = vp
+            L.ref_mibf_new.argtypes = [C.c_uint, C.c_uint64, C.c_uint, C.c_uint, C.c_double, C.POINTER(C.c_char_p),
+                                       C.c_uint]
+            L.ref_mibf_free.argtypes = [vp]
+            L.ref_mibf_filter_size.restype = C.c_uint64
+            L.ref_mibf_filter_size.argtypes = [vp]
+            L.ref_mibf_insert_bv.argtypes = [vp, C.c_char_p, C.c_size_t]
+            L.ref_mibf_get_empty.argtypes = [vp]
+            L.ref_mibf_insert_mibf.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_uint32]
+            L.ref_mibf_insert_saturation.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_uint32]
+            L.ref_mibf_stats.argtypes = [vp, u64p]
+            L.ref_mibf_bits.argtypes = [vp, u8p]
+            L.ref_mibf_data.argtypes = [vp, u32p]
+            L.ref_mibf_id_counts.restype = C.c_uint64
+            L.ref_mibf_id_counts.argtypes = [vp, u64p, C.c_size_t]
+            L.ref_mibf_at_rank.restype = C.c_size_t
+            L.ref_mibf_at_rank.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_uint, u64p, u8p, u32p, u32p, u8p, u32p,
+                                           C.c_size_t]
+            L.ref_mibf_store.argtypes = [vp, C.c_char_p]
+
+    def has_mibf(self):
+        """the miBF entry points of oracle/ref_mibf_driver.cpp are in this build"""
+        return hasattr(self.L, "ref_mibf_new")
+
     def nthash_seq(self, seq, h, k):
         s = _bytes(seq)
         cap = max(len(s), 1)
@@ -461,8 +488,94 @@ class Ref:
         def store(self, path):
             self.L.ref_cbf_store(self.p, _bytes(path))
 
+    class MIBF:
+        """MIBFConstructSupport<T, H> + its MIBloomFilter<T> (oracle/ref_mibf_driver.cpp): T by id_bytes, H =
+        ntHashIterator without seeds, stHashIterator(seeds, h2 = 1) with.  The stages in the reference's order:
+        insert_bv*, get_empty, insert_mibf*, insert_saturation*; the readers need get_empty."""
+
+        def __init__(self, ref, id_bytes, expected_entries, k, h, occupancy, seeds=None):
+            self.L = ref.L
+            seeds = list(seeds or [])
+            arr = (C.c_char_p * max(len(seeds), 1))(*[_bytes(x) for x in seeds])
+            self.p = self.L.ref_mibf_new(id_bytes, expected_entries, k, h, occupancy, arr, len(seeds))
+            if not self.p:
+                raise ValueError("ref_mibf_new: id_bytes 2 or 4; with seeds h == len(seeds)")
+            self.h = h
+
+        def close(self):
+            if self.p:
+                self.L.ref_mibf_free(self.p)
+                self.p = None
+
+        __del__ = close
+
+        def filter_size(self):
+            """calcOptimalSize(expected_entries, h, occupancy) as the constructor took it"""
+            return int(self.L.ref_mibf_filter_size(self.p))
+
+        def insert_bv(self, seq):
+            s = _bytes(seq)
+            self.L.ref_mibf_insert_bv(self.p, s, len(s))
+
+        def get_empty(self):
+            self.L.ref_mibf_get_empty(self.p)
+
+        def insert_mibf(self, seq, ident):
+            s = _bytes(seq)
+            self.L.ref_mibf_insert_mibf(self.p, s, len(s), int(ident))
+
+        def insert_saturation(self, seq, ident):
+            s = _bytes(seq)
+            self.L.ref_mibf_insert_saturation(self.p, s, len(s), int(ident))
+
+        def stats(self):
+            """[size(), getPop(), getPopNonZero(), getPopSaturated()]"""
+            out = np.zeros(4, np.uint64)
+            self.L.ref_mibf_stats(self.p, out)
+            return [int(x) for x in out]
+
+        def body(self):
+            """the bit vector as filter body bytes (bit p = bit p%8 of byte p/8), read through atRank"""
+            size = self.stats()[0]
+            bits = np.zeros(size, np.uint8)
+            self.L.ref_mibf_bits(self.p, bits)
+            return np.packbits(bits, bitorder="little")
+
+        def data(self):
+            out = np.zeros(max(self.stats()[1], 1), np.uint32)
+            self.L.ref_mibf_data(self.p, out)
+            return out[: self.stats()[1]]
+
+        def id_counts(self, n_ids):
+            """getIDCounts over a table of n_ids entries (every id in the data array must be < n_ids) ->
+            (counts, saturated)"""
+            out = np.zeros(n_ids, np.uint64)
+            sat = self.L.ref_mibf_id_counts(self.p, out, n_ids)
+            return out, int(sat)
+
+        def at_rank(self, seq, max_miss):
+            """per emitted window: pos; atRank(hashes, rankPos) -> (ok0, vals0 = data at rankPos, zeros when it
+            fails); atRank(hashes, rankPos, hits, max_miss) -> (misses returned, hits, vals = data at the hits)"""
+            s = _bytes(seq)
+            cap, h = max(len(s), 1), self.h
+            pos = np.zeros(cap, np.uint64)
+            ok0 = np.zeros(cap, np.uint8)
+            vals0 = np.zeros(cap * h, np.uint32)
+            misses = np.zeros(cap, np.uint32)
+            hits = np.zeros(cap * h, np.uint8)
+            vals = np.zeros(cap * h, np.uint32)
+            n = self.L.ref_mibf_at_rank(self.p, s, len(s), max_miss, pos, ok0, vals0, misses, hits, vals, cap)
+            return (pos[:n], ok0[:n], vals0[: n * h].reshape(n, h), misses[:n], hits[: n * h].reshape(n, h),
+                    vals[: n * h].reshape(n, h))
+
+        def store(self, path):
+            self.L.ref_mibf_store(self.p, _bytes(str(path)))
+
     def bf(self, bits=None, h=None, k=None, path=None):
         return Ref.BF(self, bits, h, k, path)
+
+    def mibf(self, id_bytes, expected_entries, k, h, occupancy, seeds=None):
+        return Ref.MIBF(self, id_bytes, expected_entries, k, h, occupancy, seeds)
 
     def cbf(self, nbytes=None, h=None, k=None, thr=1, path=None):
         return Ref.CBF(self, nbytes, h, k, thr, path)

@@ -1,0 +1,2 @@
+// oracle/standin/sdsl/rank_support.hpp -- STAND-IN, TEST INFRASTRUCTURE ONLY: empty on purpose.  The reference's miBF headers include
+// this name; nothing they use comes from it (see sdsl/bit_vector_il.hpp and google/dense_hash_set beside it).

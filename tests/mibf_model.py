@@ -1,7 +1,8 @@
 """numpy restatement of the reference's multi-index Bloom filter (miBF) stages 3-4, the checker of tests/test_gpu_mibf.py
 and tests/test_mibf_cpu.py.  Written from the reference's text (MIBloomFilter.hpp, MIBFConstructSupport.hpp,
-MIBFQuerySupport.hpp); sdsl-lite and google sparsehash are not available, so rank() is a cumulative sum over the
-stage-1 bit vector and the dense_hash_set walk is the ascending order this library documents (include/btlbf.h).
+MIBFQuerySupport.hpp) and pinned to the reference's own build by tests/test_mibf_vs_ref.py (oracle/ref_mibf_driver.cpp).
+rank() is a cumulative sum over the stage-1 bit vector and the dense_hash_set walk is the ascending order this library
+documents (include/btlbf.h).
 Inputs are hash rows as btlbf_hash_seqs emits them (hash_seqs / sthash_seqs): window p of the buffer at row p, valid
 bit p set iff the iterator emits the window."""
 import struct

@@ -31,19 +31,19 @@ def ragged(rng, n, lo=40, hi=200, n_rate=0.01):
     return seq, starts
 
 
-def stage1(bf, bits, h, seeds, seq, starts=None, read_len=0):
-    f = bf.BloomFilter(bits, h, K)
+def stage1(bf, bits, h, seeds, seq, starts=None, read_len=0, k=K):
+    f = bf.BloomFilter(bits, h, k)
     if seeds:
         f.setSpacedSeeds(seeds, 1)
     f.insertSeqs(seq, starts=starts, read_len=read_len)
     return f
 
 
-def rows_of(bf, seq, h, seeds, starts=None, read_len=0):
+def rows_of(bf, seq, h, seeds, starts=None, read_len=0, k=K):
     if seeds:
-        hv, valid, _ = bf.sthash_seqs(seq, seeds, 1, K, starts=starts, read_len=read_len)
+        hv, valid, _ = bf.sthash_seqs(seq, seeds, 1, k, starts=starts, read_len=read_len)
     else:
-        hv, valid = bf.hash_seqs(seq, h, K, starts=starts, read_len=read_len)
+        hv, valid = bf.hash_seqs(seq, h, k, starts=starts, read_len=read_len)
     n = len(seq)
     return np.asarray(hv)[:n].astype(np.uint64), bf.bits_to_bool(valid, n)
 
@@ -255,3 +255,207 @@ def test_spaced_seeds_need_h2_one(bf):
     with pytest.raises(BtlbfError) as e:
         bf.MIBloomFilter(f, 2)
     assert e.value.code == 1
+
+
+# ---- edges: layouts, memory spaces, degenerate buffers, parameter limits, the counter's wrap ----------------------------
+
+
+def three_ops(bf, m, ranks, data, counts, seq, ids, h, seeds, id_bytes, serial, max_misses, starts=None, read_len=0,
+              device=False, k=K):
+    """insertIDs, insertSaturation and query of one buffer on the miBF `m`, each against the model continued from
+    (data, counts), which are updated in place; the buffer, its starts and its ids live on the device with device=True"""
+    import torch
+
+    seq = np.ascontiguousarray(seq, np.uint8)
+    ids = np.asarray(ids, np.int64)
+    rows, valid = rows_of(bf, seq, h, seeds, starts=starts, read_len=read_len, k=k)
+    rows = rows.reshape(len(seq), h)
+    wseq = mm.window_seqs(len(seq), starts, read_len)
+    if device:
+        dseq = torch.from_numpy(seq).cuda()
+        dids = torch.from_numpy(ids.astype(np.int32)).cuda()
+        dst = None if starts is None else torch.from_numpy(np.asarray(starts).astype(np.int64)).cuda()
+    else:
+        dseq, dids, dst = seq, ids, starts
+    m.insertIDs(dseq, dids, starts=dst, read_len=read_len)
+    mm.insert_ids(data, counts, ranks, rows, valid, wseq, ids, id_bytes)
+    assert (m.counts().astype(np.int64) == counts).all()
+    assert (m.data().astype(np.int64) == data).all()
+    got = m.insertSaturation(dseq, dids, starts=dst, read_len=read_len, serial=serial)
+    exp = (mm.saturate_serial if serial else mm.saturate_parallel)(data, counts, ranks, rows, valid, wseq, ids, id_bytes)
+    assert [got["clean"], got["found"], got["mutated"], got["saturated"]] == exp
+    assert (m.counts().astype(np.int64) == counts).all()
+    assert (m.data().astype(np.int64) == data).all()
+    return exp, query_check(bf, m, ranks, data, seq, h, seeds, max_misses, starts=starts, read_len=read_len,
+                            device=device, k=k)
+
+
+def query_check(bf, m, ranks, data, seq, h, seeds, max_misses, starts=None, read_len=0, device=False, k=K):
+    """query of one buffer for every max_miss against the model over `data` -> matching windows per max_miss"""
+    import torch
+
+    seq = np.ascontiguousarray(seq, np.uint8)
+    rows, valid = rows_of(bf, seq, h, seeds, starts=starts, read_len=read_len, k=k)
+    rows = rows.reshape(len(seq), h)
+    dseq, dst = seq, starts
+    if device:
+        dseq = torch.from_numpy(seq).cuda()
+        dst = None if starts is None else torch.from_numpy(np.asarray(starts).astype(np.int64)).cuda()
+    n_match = []
+    for mx in max_misses:
+        vals, hit, vb, cnt = m.query(dseq, max_miss=mx, starts=dst, read_len=read_len, want_counts=True)
+        if device:
+            vals, hit, vb, cnt = (x.cpu().numpy() for x in (vals, hit, vb, cnt))
+        ev, match = mm.query(data, ranks, rows, valid, mx, bool(seeds))
+        assert (bf.bits_to_bool(vb, len(seq)) == valid).all()
+        assert (bf.bits_to_bool(hit, len(seq)) == match).all()
+        assert (np.asarray(vals).view(m.dtype).reshape(len(seq), h).astype(np.int64) == ev).all()
+        assert [int(x) for x in cnt] == [int(valid.sum()), int(match.sum())]
+        n_match.append(int(match.sum()))
+    return n_match
+
+
+@pytest.mark.parametrize("serial", [True, False], ids=["serial", "parallel"])
+@pytest.mark.parametrize("layout,device", [("uniform", False), ("uniform", True), ("ragged", True)],
+                         ids=["uniform-host", "uniform-device", "ragged-device"])
+def test_layouts_and_device_inputs(bf, layout, device, serial):
+    """the uniform layout and device-resident buffers through insertSaturation and query too (dense: all three outcomes);
+    the query also over foreign sequences in the same layout, where max_miss changes the answer"""
+    rng = np.random.RandomState(29)
+    if layout == "uniform":
+        L, n = 100, 300
+        seq, starts = ragged(rng, n, L, L + 1, 0.005)
+    else:
+        L, n = 0, 300
+        seq, starts = ragged(rng, n, 40, 160, 0.005)
+    ids = rng.randint(1, 50, n)
+    foreign, fst = ragged(rng, 60, L or 40, L + 1 if L else 160, 0.02)
+    q, qst = np.concatenate([seq, foreign]), np.concatenate([starts, fst[1:] + starts[-1]]).astype(np.uint64)
+    if L:
+        starts = qst = None
+    bits = 1 << 15
+    f = stage1(bf, bits, 4, C5_SEEDS, seq, starts=starts, read_len=L)
+    ranks = mm.Ranks(f.download(), bits)
+    m = bf.MIBloomFilter(f, 2)
+    data, counts = model_state(m)
+    exp, n_match = three_ops(bf, m, ranks, data, counts, seq, ids, 4, C5_SEEDS, 2, serial, (0, 2), starts=starts,
+                             read_len=L, device=device)
+    assert min(exp[1:]) >= 0.01 * exp[0]
+    assert n_match == [exp[0]] * 2  # every bit of an inserted window is set: max_miss cannot matter here
+    n_match = query_check(bf, m, ranks, data, q, 4, C5_SEEDS, (0, 1, 2), starts=qst, read_len=L, device=device)
+    assert len(set(n_match)) == 3
+
+
+def _degenerate(name, rng):
+    """-> (buffer, starts or None, read_len)"""
+    real = lambda n: np.frombuffer(b"ACGT", np.uint8)[rng.randint(0, 4, n)].copy()  # noqa: E731
+    if name == "empty":
+        return np.zeros(0, np.uint8), np.zeros(2, np.uint64), 0  # no byte at all: one sequence of length zero
+    if name == "shorter_than_k":
+        lens = rng.randint(0, K, 50)
+        return real(int(lens.sum())), np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64), 0
+    if name == "only_n":
+        return np.full(500, ord("N"), np.uint8), np.array([0, 100, 131, 500], np.uint64), 0
+    if name == "only_n_uniform":
+        return np.full(500, ord("N"), np.uint8), None, 50
+    if name == "zero_length_between":
+        return real(200), np.array([0, 90, 90, 200], np.uint64), 0
+    assert name == "read_len_k"
+    return real(40 * K), None, K
+
+
+@pytest.mark.parametrize("serial", [True, False], ids=["serial", "parallel"])
+@pytest.mark.parametrize("name", ["empty", "shorter_than_k", "only_n", "only_n_uniform", "zero_length_between",
+                                  "read_len_k"])
+def test_degenerate_buffers(bf, name, serial):
+    """buffers with no clean window leave data and counts as they were and count nothing; a zero-length sequence keeps
+    its id out of its neighbours' windows; read_len = k is one window per sequence"""
+    rng = np.random.RandomState(31)
+    base, bst = ragged(rng, 80, 60, 120, 0.005)
+    buf, starts, L = _degenerate(name, rng)
+    bits = 1 << 12
+    f = stage1(bf, bits, 4, C5_SEEDS, base, starts=bst)
+    if len(buf):
+        f.insertSeqs(buf, starts=starts, read_len=L)
+    ranks = mm.Ranks(f.download(), bits)
+    m = bf.MIBloomFilter(f, 2)
+    data, counts = model_state(m)
+    bids = rng.randint(1, 30, 80)
+    three_ops(bf, m, ranks, data, counts, base, bids, 4, C5_SEEDS, 2, serial, (1,), starts=bst)
+    before = data.copy(), counts.copy()
+    n_seqs = len(starts) - 1 if starts is not None else len(buf) // L
+    ids = rng.randint(30, 60, n_seqs)
+    exp, n_match = three_ops(bf, m, ranks, data, counts, buf, ids, 4, C5_SEEDS, 2, serial, (0, 1), starts=starts,
+                             read_len=L)
+    if name in ("zero_length_between", "read_len_k"):
+        assert exp[0] == (200 - 2 * (K - 1) if name == "zero_length_between" else 40)
+        assert (counts != before[1]).any()
+    else:
+        assert exp == [0, 0, 0, 0] and n_match == [0, 0]
+        assert (data == before[0]).all() and (counts == before[1]).all()  # and three_ops compared the device's with them
+
+
+@pytest.mark.parametrize("seeds,h,k,max_misses", [(None, 1, K, (0, 3)), (C5_SEEDS, 4, K, (3, 4, 5, 1 << 30)),
+                                                  (None, 3, 32, (0,)), (None, 3, 33, (0,))],
+                         ids=["nthash1", "C5-max_miss>=h", "nthash-k32", "nthash-k33"])
+@pytest.mark.parametrize("id_bytes", [2, 4])
+def test_parameter_edges(bf, seeds, h, k, max_misses, id_bytes):
+    """one hash without seeds; max_miss at and beyond h with seeds (every clean window matches); k on both sides of the
+    32 / 33 boundary of ntHash's split rotation"""
+    rng = np.random.RandomState(37 + k + h)
+    seq, starts = ragged(rng, 200, 40, 160, 0.01)
+    bits = (1 << 13) * h
+    f = stage1(bf, bits, h, seeds, seq, starts=starts, k=k)
+    ranks = mm.Ranks(f.download(), bits)
+    m = bf.MIBloomFilter(f, id_bytes)
+    assert m.getHashNum() == h and m.getKmerSize() == k
+    data, counts = model_state(m)
+    ids = rng.randint(1, 40, 200)
+    three_ops(bf, m, ranks, data, counts, seq, ids, h, seeds, id_bytes, True, (0,), starts=starts, k=k)
+    foreign, fst = ragged(rng, 60, 40, 160, 0.02)
+    rows, valid = rows_of(bf, foreign, h, seeds, starts=fst, k=k)
+    for mx in max_misses:
+        vals, hit, vb, cnt = m.query(foreign, max_miss=mx, starts=fst, want_counts=True)
+        ev, match = mm.query(data, ranks, rows, valid, mx, bool(seeds))
+        assert (bf.bits_to_bool(vb, len(foreign)) == valid).all()
+        assert (bf.bits_to_bool(hit, len(foreign)) == match).all()
+        assert (np.asarray(vals).astype(np.int64) == ev).all()
+        assert cnt.tolist() == [int(valid.sum()), int(match.sum())]
+        if seeds and mx >= h:
+            assert (match == valid).all() and 0 < (ev != 0).sum() < ev.size
+        else:
+            assert 0 < match.sum() < valid.sum()
+
+
+def test_insert_ids_counter_wrap_u16(bf):
+    """uint16_t counts that wrap: a 64-bit stage-1 filter (64 ranks) under 9200 reads of 150 bases, whose 4.4 * 10^6
+    distinct hash values give every rank more than 65 535 arrivals (at least 68 350 each: counted on the CPU from the
+    same generator).  A count that wraps to 0 replaces nothing, and the next arrival counts as the first
+    (include/btlbf.h).  One call, and three calls under a scratch budget of a few hundred reads per batch."""
+    import torch
+
+    n, L, bits = 9200, 150, 64
+    reads = bf.synth_reads_device(23, 0, n, L)
+    f = stage1(bf, bits, 4, C5_SEEDS, reads[: 100 * L], read_len=L)
+    torch.cuda.synchronize()
+    ranks = mm.Ranks(f.download(), bits)
+    assert ranks.pop == 64
+    ids = (np.arange(n) // 100 + 1).astype(np.uint32)
+    dids = torch.from_numpy(ids.astype(np.int32)).cuda()
+    host = reads.cpu().numpy()
+    rows, valid = rows_of(bf, host, 4, C5_SEEDS, read_len=L)
+    arrivals = np.bincount(ranks.rank(np.unique(rows[valid].ravel())), minlength=64)  # distinct values alone
+    assert arrivals.min() > 65535  # from the model's inputs alone: every one of the 64 counts wraps
+    data, counts = np.zeros(64, np.int64), np.zeros(64, np.int64)
+    mm.insert_ids(data, counts, ranks, rows, valid, mm.window_seqs(len(host), read_len=L), ids, 2)
+    assert (counts < arrivals).all()
+    a = bf.MIBloomFilter(f, 2)
+    a.insertIDs(reads, dids, read_len=L)
+    assert (a.counts().astype(np.int64) == counts).all()
+    assert (a.data().astype(np.int64) == data).all()
+    b = bf.MIBloomFilter(f, 2)
+    b.setScratchBudget(8 << 20)
+    for lo, hi in ((0, 3000), (3000, 3001), (3001, n)):
+        b.insertIDs(reads[lo * L:hi * L], dids[lo:hi], read_len=L)
+    assert (b.counts().astype(np.int64) == counts).all()
+    assert (b.data().astype(np.int64) == data).all()

@@ -79,3 +79,50 @@ def test_rank_over_the_mibf_stage1_filter(bf):
     assert len(np.unique(r[first])) == len(up)  # rank is injective on set bits
     order = np.argsort(up)
     assert (np.diff(r[first][order].astype(np.int64)) > 0).all()  # and monotone in the position
+
+
+def test_rank_beyond_2_pow_32_bits(bf):
+    """positions and ranks past 2^32: a sparse filter of 2^32 + 192 bits (the miBF sits on this structure), against a
+    block-wise popcount of the downloaded words"""
+    import torch
+
+    bits, k = (1 << 32) + 192, 31
+    reads = bf.synth_reads_device(7, 0, 20000, 150)
+    f = bf.BloomFilter(bits, 4, k)
+    f.insertSeqs(reads, read_len=150)
+    top = np.array([[(1 << 32) - 1, 1 << 32, (1 << 32) + 64, (1 << 32) + 191]], np.uint64)  # hash % size = itself
+    f.insert(top)
+    torch.cuda.synchronize()
+    body = f.download()
+    assert body.size == bits // 8
+    body = np.concatenate([body, np.zeros(-body.size % 64, np.uint8)])  # whole 512-bit blocks
+    blocks = np.bitwise_count(body.view(np.uint64)).reshape(-1, 8).sum(axis=1, dtype=np.uint64)
+    before = np.concatenate([[0], np.cumsum(blocks, dtype=np.uint64)])
+    ones = int(before[-1])
+    assert 8 * 10**6 < ones < 10**7
+
+    def expect(pos):
+        p = np.asarray(pos, np.uint64).astype(np.int64)
+        blk = p >> 9
+        b = np.unpackbits(body[blk[:, None] * 64 + np.arange(64)], axis=1, bitorder="little")
+        inside = np.concatenate([np.zeros((len(p), 1), np.uint64), np.cumsum(b, axis=1, dtype=np.uint64)], axis=1)
+        return before[blk] + inside[np.arange(len(p)), p & 511], b[np.arange(len(p)), p & 511]
+
+    rs = bf.RankSupport(f)
+    assert rs.ones() == ones
+    last = (int(np.flatnonzero(body)[-1]) << 3) + int(body[np.flatnonzero(body)[-1]]).bit_length() - 1
+    assert last == (1 << 32) + 191
+    rng = np.random.RandomState(3)
+    pos = np.concatenate([[0, bits - 1, last, (1 << 32) - 1, 1 << 32, (1 << 32) + 1, (1 << 32) + 64, (1 << 32) + 65,
+                           (1 << 31) - 1, 1 << 31], (1 << 32) - 1 - rng.randint(0, 1 << 20, 500),
+                          (1 << 32) + rng.randint(0, 192, 100), rng.randint(0, bits, 2000)]).astype(np.uint64)
+    r, bit = rs.rank(pos)
+    er, eb = expect(pos)
+    assert (r == er).all() and (bit == eb).all()
+    assert int(r[2]) == ones - 1 and bit[2] == 1  # the last set bit
+    # hash values that reduce to positions on both sides of 2^32
+    hv = pos + np.uint64(bits) * rng.randint(1, 1 << 30, pos.size).astype(np.uint64)
+    r, bit = rs.rank(hv, hashes=True)
+    assert (r == er).all() and (bit == eb).all()
+    m = bf.MIBloomFilter(f, 2)
+    assert m.getPop() == ones and m.size() == bits

@@ -25,3 +25,12 @@ RT=$(/opt/rocm/lib/llvm/bin/clang -print-file-name=libclang_rt.asan-x86_64.so)
 echo "runtime: $RT"
 LD_PRELOAD=$RT ASAN_OPTIONS=detect_leaks=0:halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
 	BTLBF_LIB=$ROOT/$P/libbtlbf_asan.so python3 -m pytest tests/test_fastx.py tests/test_abi_cpu.py -q -m "not gpu" -p no:cacheprovider
+# the test-only reference miBF driver (oracle/ref_mibf_driver.cpp over oracle/standin/), instrumented the same way, under
+# the test that drives it -- only where the reference tree is there to build it from.  (tests/test_oracle_vs_ref.py is
+# not run this way: its raw k-mer case calls the reference where it reads past its own 2-/3-mer tables.)
+if make -C oracle _ref/libbtlref_asan.so > /dev/null 2>&1; then
+	LD_PRELOAD=$RT ASAN_OPTIONS=detect_leaks=0:halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
+		BTLBF_REF_SO=$ROOT/oracle/_ref/libbtlref_asan.so python3 -m pytest tests/test_mibf_vs_ref.py -q -m "not gpu" -p no:cacheprovider
+else
+	echo "reference driver: not built here (no reference tree), skipped"
+fi
