@@ -33,6 +33,11 @@ class FastxStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class MibfClassifyParams(C.Structure):
+    _fields_ = [("extra_count", C.c_double), ("extra_frame_limit", C.c_uint32), ("max_miss", C.c_uint32),
+                ("min_count", C.c_uint32), ("best_hit_agree", C.c_uint32), ("max_results", C.c_uint32)]
+
+
 class BtlbfError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("btlbf error %d: %s" % (code, msg))
@@ -97,6 +102,9 @@ _PROTOS = {
     "btlbf_mibf_insert_ids_seqs": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(Layout), _P, C.c_int, _P]),
     "btlbf_mibf_saturate_seqs": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(Layout), _P, C.c_int, _P, C.c_int, _P]),
     "btlbf_mibf_query_seqs": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(Layout), C.c_uint, _P, _P, _P, _P, C.c_int, _P]),
+    "btlbf_mibf_classify_seqs": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(Layout), C.POINTER(MibfClassifyParams), _P, _P,
+                                           C.c_uint64, _P, _P, _P, _P, C.c_int, _P]),
+    "btlbf_mibf_classify_paths": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "btlbf_mibf_stats": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "btlbf_mibf_id_counts": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "btlbf_mibf_download": (C.c_int, [_P, _P]),

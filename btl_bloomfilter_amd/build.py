@@ -18,7 +18,7 @@ HEADERS = ["internal.hpp", "host_internal.hpp", "device_utils.hpp", "seq_core.hp
            os.path.join("..", "..", "include", "btlbf.h")]
 # host units (the C ABI over host_internal.hpp) and kernel units; tools/sanitize_host.sh reads both lists
 HOST_UNITS = ["capi", "host_io", "host_seq", "host_partition", "host_aux", "host_mibf", "fastx"]
-KERNEL_UNITS = ["seq_kernels", "aux_kernels", "partition_kernels", "mibf_kernels"]
+KERNEL_UNITS = ["seq_kernels", "aux_kernels", "partition_kernels", "mibf_kernels", "mibf_classify_kernels"]
 # (object name, source, extra flags): pass A of the partitioned pipeline is one unit per hash count
 UNITS = [(u, u + ".cpp", []) for u in HOST_UNITS] + [(u, u + ".hip", []) for u in KERNEL_UNITS]
 UNITS += [("part_hash_h%d" % h, "part_hash_inst.hip", ["-DBTLBF_PART_H=%d" % h]) for h in range(1, 9)]

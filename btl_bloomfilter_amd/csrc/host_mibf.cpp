@@ -32,7 +32,11 @@ struct btlbf_mibf {
 	void* d_counts = nullptr; // pop T
 	uint64_t* d_pos_tab = nullptr;
 	uint16_t* d_dc_idx = nullptr;
-	unsigned long long* d_stat = nullptr; // 4 x u64
+	unsigned long long* d_stat = nullptr; // 8 x u64: [0..3] call counters, [4] classify's largest id, [5..6] its table paths
+	// classify: the largest m_counts index over the data array, valid until the array next changes
+	bool max_id_known = false;
+	uint64_t max_id = 0;
+	uint64_t cls_paths[2] = {0, 0}; // the last classify call: sequences walked over an LDS / a global table
 };
 
 namespace {
@@ -138,11 +142,11 @@ struct MibfCall {
 };
 
 int mibf_prepare(MibfCall& c, const char* seq, uint64_t len, const btlbf_layout* layout, const uint32_t* ids, int mem,
-                 hipStream_t s)
+                 hipStream_t s, bool want_ids = true)
 {
 	if (!layout || (!layout->starts && !layout->read_len))
 		return fail(BTLBF_EINVAL, "miBF: a layout (read_len or starts) gives every sequence its id");
-	if (!ids)
+	if (!ids && want_ids)
 		return fail(BTLBF_EINVAL, "miBF: null ids");
 	int rc = make_view(c.v, seq, len, layout, mem, s);
 	if (rc)
@@ -163,6 +167,8 @@ int mibf_prepare(MibfCall& c, const char* seq, uint64_t len, const btlbf_layout*
 		c.L = layout->read_len;
 		c.n_seqs = len / c.L;
 	}
+	if (!want_ids)
+		return BTLBF_OK;
 	if (mem == BTLBF_DEVICE) {
 		c.d_ids = ids;
 	} else {
@@ -301,6 +307,7 @@ extern "C" int btlbf_mibf_insert_ids_seqs(btlbf_mibf* m, const char* seq, uint64
 		return rc;
 	if (len == 0 || c.n_seqs == 0)
 		return BTLBF_OK;
+	m->max_id_known = false;
 	// one batch: 4 x 8 bytes per hash value (keys, values, and the sort's output) + the sort's scratch
 	const uint64_t budget = m->budget ? m->budget : kMibfDefaultScratch;
 	const uint64_t max_bytes = std::max<uint64_t>(1, budget / (40ull * m->h));
@@ -364,6 +371,7 @@ extern "C" int btlbf_mibf_saturate_seqs(btlbf_mibf* m, const char* seq, uint64_t
 	if (rc)
 		return rc;
 	const uint64_t budget = m->budget ? m->budget : kMibfDefaultScratch;
+	m->max_id_known = false;
 	HIP_TRY(hipMemsetAsync(m->d_stat, 0, 32, s));
 	if (order == BTLBF_ORDER_SERIAL) {
 		// hash rows of a batch (8 bytes per hash value + the window bitmap), then one lane in buffer order
@@ -490,6 +498,187 @@ extern "C" int btlbf_mibf_query_seqs(btlbf_mibf* m, const char* seq, uint64_t le
 	return BTLBF_OK;
 }
 
+// MIBFQuerySupport<T>::query (MIBFQuerySupport.hpp:95-109) of every sequence: phase 1 is the MIBF_QUERY launch of
+// btlbf_mibf_query_seqs into scratch, phase 2 the walk of mibf_classify_kernels.hip, batch by batch under the budget
+extern "C" int btlbf_mibf_classify_seqs(btlbf_mibf* m, const char* seq, uint64_t len, const btlbf_layout* layout,
+                                        const btlbf_mibf_classify_params* p, const double* per_frame_prob,
+                                        const uint32_t* min_count_per_id, uint64_t n_ids, btlbf_mibf_hit* hits,
+                                        uint32_t* n_hits, uint32_t* sat_count, uint32_t* eval_count, int mem, void* stream)
+{
+	if (!m || (!seq && len) || !layout || !p || !per_frame_prob || !min_count_per_id || !hits || !n_hits || !sat_count ||
+	    !eval_count)
+		return fail(BTLBF_EINVAL, "null argument");
+	if (p->max_results == 0)
+		return fail(BTLBF_EINVAL, "miBF classify: max_results must be at least 1");
+	if (n_ids == 0 || n_ids > (1ull << (m->id_bytes * 8 - 1)))
+		return fail(BTLBF_EINVAL, "miBF classify: n_ids must be 1..2^%u for %u-byte ids, not %llu", m->id_bytes * 8 - 1,
+		            m->id_bytes, (unsigned long long)n_ids);
+	std::lock_guard<std::mutex> lk(m->mu);
+	DeviceGuard g(m->device);
+	hipStream_t s = static_cast<hipStream_t>(stream);
+	MibfCall c;
+	int rc = mibf_prepare(c, seq, len, layout, nullptr, mem, s, false);
+	if (rc)
+		return rc;
+	m->cls_paths[0] = m->cls_paths[1] = 0;
+	if (c.n_seqs == 0)
+		return BTLBF_OK;
+	// every index the walk will use lies inside the caller's tables
+	if (!m->max_id_known) {
+		HIP_TRY(hipMemsetAsync(m->d_stat + 4, 0, 8, s));
+		HIP_TRY(launch_mibf_classify_maxid(m->id_bytes, m->d_data, m->pop, m->d_stat + 4, s));
+		unsigned long long mx = 0;
+		HIP_TRY(hipMemcpyAsync(&mx, m->d_stat + 4, 8, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		m->max_id = mx;
+		m->max_id_known = true;
+	}
+	if (m->max_id >= n_ids)
+		return fail(BTLBF_EINVAL, "miBF classify: the ID array holds id %llu, the tables %llu entries; nothing was written",
+		            (unsigned long long)m->max_id, (unsigned long long)n_ids);
+	// batches: per byte h values, the hit mask and two bitmap bits; per sequence whose table does not fit LDS, the table
+	const uint64_t budget = m->budget ? m->budget : kMibfDefaultScratch;
+	const uint64_t per_byte = (uint64_t)m->h * m->id_bytes + 2;
+	struct Batch {
+		uint64_t s0, s1, big, slots;
+	};
+	std::vector<Batch> batches;
+	uint64_t cap_bytes = 0, cap_big = 0, cap_slots = 0;
+	auto seq_cost = [&](uint64_t i, uint64_t* slots) {
+		const uint64_t n = c.start(i + 1) - c.start(i);
+		const uint32_t cap = mibf_classify_cap(n, m->k, m->h, n_ids);
+		*slots = cap > kMibfClsLdsSlots ? cap : 0;
+		return n * per_byte + 64 + *slots * kMibfClsSlotWords * 4 + (*slots ? 12 : 0);
+	};
+	for (uint64_t s0 = 0; s0 < c.n_seqs;) {
+		Batch b{s0, s0, 0, 0};
+		uint64_t used = 0;
+		while (b.s1 < c.n_seqs && b.s1 - b.s0 < 0x7fffffffull) {
+			uint64_t slots;
+			const uint64_t cost = seq_cost(b.s1, &slots);
+			if (used + cost > budget)
+				break;
+			used += cost;
+			b.big += slots != 0;
+			b.slots += slots;
+			++b.s1;
+		}
+		if (b.s1 == b.s0)
+			return fail(BTLBF_ENOMEM, "miBF classify: sequence %llu does not fit the scratch budget (btlbf_mibf_set_scratch); "
+			            "nothing was written", (unsigned long long)s0);
+		cap_bytes = std::max(cap_bytes, c.start(b.s1) - c.start(b.s0));
+		cap_big = std::max(cap_big, b.big);
+		cap_slots = std::max(cap_slots, b.slots);
+		batches.push_back(b);
+		s0 = b.s1;
+	}
+	DevBuf vals, hit, valid, masks, big_list, big_off, big_tab, tables;
+	if (vals.alloc(cap_bytes * m->h * m->id_bytes) || hit.alloc(bitmap_bytes(cap_bytes)) || valid.alloc(bitmap_bytes(cap_bytes)) ||
+	    masks.alloc(cap_bytes) || big_list.alloc(cap_big * 4) || big_off.alloc(cap_big * 8) ||
+	    big_tab.alloc(cap_slots * kMibfClsSlotWords * 4)) {
+		(void)hipGetLastError();
+		return fail(BTLBF_ENOMEM, "miBF classify: scratch of %llu bytes", (unsigned long long)budget);
+	}
+	const double* d_prob = per_frame_prob;
+	const uint32_t* d_minc = min_count_per_id;
+	if (mem != BTLBF_DEVICE) {
+		HIP_TRY(tables.alloc(n_ids * 12));
+		HIP_TRY(hipMemcpyAsync(tables.p, per_frame_prob, n_ids * 8, hipMemcpyHostToDevice, s));
+		HIP_TRY(hipMemcpyAsync(tables.as<uint8_t>() + n_ids * 8, min_count_per_id, n_ids * 4, hipMemcpyHostToDevice, s));
+		d_prob = tables.as<double>();
+		d_minc = reinterpret_cast<const uint32_t*>(tables.as<uint8_t>() + n_ids * 8);
+	}
+	OutBuf o_hits, o_n, o_sat, o_eval;
+	if ((rc = o_hits.prepare(hits, c.n_seqs * p->max_results * sizeof(btlbf_mibf_hit), mem, true, s)) ||
+	    (rc = o_n.prepare(n_hits, c.n_seqs * 4, mem, true, s)) || (rc = o_sat.prepare(sat_count, c.n_seqs * 4, mem, true, s)) ||
+	    (rc = o_eval.prepare(eval_count, c.n_seqs * 4, mem, true, s)))
+		return rc;
+	HIP_TRY(hipMemsetAsync(m->d_stat, 0, 32, s));
+	HIP_TRY(hipMemsetAsync(m->d_stat + 5, 0, 16, s));
+	std::vector<uint32_t> h_list;
+	std::vector<uint64_t> h_off;
+	for (const Batch& b : batches) {
+		const uint64_t b0 = c.start(b.s0), blen = c.start(b.s1) - b0;
+		DevBuf sb;
+		LayoutParams lay;
+		if ((rc = mibf_batch_layout(c, b.s0, b.s1, sb, lay, s)))
+			return rc;
+		if (blen) {
+			MibfArgs a = mibf_args(m, c.v.d_seq + b0, blen, lay);
+			a.max_miss = p->max_miss;
+			a.values = vals.p;
+			a.hit_bits = hit.as<uint8_t>();
+			a.valid_bits = valid.as<uint8_t>();
+			a.hit_masks = masks.as<uint8_t>();
+			a.stat = m->d_stat;
+			HIP_TRY(launch_mibf_seq(2 /* MIBF_QUERY */, m->id_bytes, a, s));
+		}
+		MibfClassifyArgs q;
+		memset(&q, 0, sizeof q);
+		q.values = vals.p;
+		q.valid_bits = valid.as<uint64_t>();
+		q.match_bits = hit.as<uint64_t>();
+		q.hit_masks = masks.as<uint8_t>();
+		q.layout = lay;
+		q.h = m->h;
+		q.k = m->k;
+		q.spaced = m->hp.n_seeds ? 1 : 0;
+		q.extra_frame_limit = p->extra_frame_limit;
+		q.min_count = p->min_count;
+		q.best_hit_agree = p->best_hit_agree;
+		q.max_results = p->max_results;
+		q.extra_count = p->extra_count;
+		q.per_frame_prob = d_prob;
+		q.min_count_per_id = d_minc;
+		q.n_ids = n_ids;
+		q.hits = o_hits.d;
+		q.n_hits = static_cast<uint32_t*>(o_n.d);
+		q.sat_count = static_cast<uint32_t*>(o_sat.d);
+		q.eval_count = static_cast<uint32_t*>(o_eval.d);
+		q.row0 = b.s0;
+		q.stat = m->d_stat + 5;
+		if (b.big) {
+			h_list.clear();
+			h_off.clear();
+			uint64_t off = 0;
+			for (uint64_t i = b.s0; i < b.s1; ++i) {
+				const uint32_t cap = mibf_classify_cap(c.start(i + 1) - c.start(i), m->k, m->h, n_ids);
+				if (cap > kMibfClsLdsSlots) {
+					h_list.push_back((uint32_t)(i - b.s0));
+					h_off.push_back(off);
+					off += cap;
+				}
+			}
+			HIP_TRY(hipMemcpyAsync(big_list.p, h_list.data(), h_list.size() * 4, hipMemcpyHostToDevice, s));
+			HIP_TRY(hipMemcpyAsync(big_off.p, h_off.data(), h_off.size() * 8, hipMemcpyHostToDevice, s));
+			HIP_TRY(hipStreamSynchronize(s)); // the two vectors are reused by the next batch
+			q.big_list = big_list.as<uint32_t>();
+			q.big_off = big_off.as<uint64_t>();
+			q.big_tab = big_tab.as<uint32_t>();
+			q.n_big = b.big;
+		}
+		HIP_TRY(launch_mibf_classify(m->id_bytes, q, s));
+	}
+	unsigned long long paths[2] = {0, 0};
+	HIP_TRY(hipMemcpyAsync(paths, m->d_stat + 5, 16, hipMemcpyDeviceToHost, s));
+	if ((rc = o_hits.finish(s)) || (rc = o_n.finish(s)) || (rc = o_sat.finish(s)) || (rc = o_eval.finish(s)))
+		return rc;
+	HIP_TRY(hipStreamSynchronize(s)); // scratch is freed on return
+	m->cls_paths[0] = paths[0];
+	m->cls_paths[1] = paths[1];
+	return BTLBF_OK;
+}
+
+extern "C" int btlbf_mibf_classify_paths(btlbf_mibf* m, uint64_t* out2)
+{
+	if (!m || !out2)
+		return fail(BTLBF_EINVAL, "null argument");
+	std::lock_guard<std::mutex> lk(m->mu);
+	out2[0] = m->cls_paths[0];
+	out2[1] = m->cls_paths[1];
+	return BTLBF_OK;
+}
+
 extern "C" int btlbf_mibf_stats(btlbf_mibf* m, uint64_t* out3)
 {
 	if (!m || !out3)
@@ -547,6 +736,7 @@ extern "C" int btlbf_mibf_upload(btlbf_mibf* m, const void* host_src)
 		return fail(BTLBF_EINVAL, "null argument");
 	std::lock_guard<std::mutex> lk(m->mu);
 	DeviceGuard g(m->device);
+	m->max_id_known = false;
 	HIP_TRY(hipMemcpy(m->d_data, host_src, m->pop * m->id_bytes, hipMemcpyHostToDevice));
 	return BTLBF_OK;
 }

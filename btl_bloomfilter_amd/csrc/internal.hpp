@@ -322,6 +322,7 @@ struct MibfArgs {
 	uint8_t* hit_bits;
 	uint8_t* valid_bits;
 	unsigned long long* stat; // {clean, found | matched, mutated, saturated}
+	uint8_t* hit_masks;       // MIBF_QUERY, optional: per window, bit i = hash i found its bit set (m_hits) in a matched window
 };
 hipError_t launch_mibf_seq(int op, int id_bytes, const MibfArgs& a, hipStream_t s);
 hipError_t mibf_sort_temp_bytes(uint64_t n, size_t* bytes);
@@ -339,5 +340,45 @@ hipError_t launch_mibf_serial_saturate(int id_bytes, const uint64_t* rows, const
 hipError_t launch_mibf_stats(int id_bytes, const void* data, uint64_t n, unsigned long long* out2, hipStream_t s);
 hipError_t launch_mibf_hist(int id_bytes, const void* data, uint64_t n, uint64_t n_bins, unsigned long long* bins,
                             hipStream_t s);
+
+// read classification over the miBF (mibf_classify_kernels.hip): MIBFQuerySupport<T>::query of every sequence of a batch
+// on the outputs of MIBF_QUERY.  A sequence's counts live in an open-addressed table of mibf_classify_cap() slots.
+static constexpr uint32_t kMibfClsMaxHash = 8;
+static constexpr uint32_t kMibfClsSlotWords = 6;  // uint32_t per table slot
+static constexpr uint32_t kMibfClsLdsSlots = 256; // tables up to this size are kept in LDS (6 KiB per wavefront)
+// slots for a sequence of `bytes` bytes: a power of two above min(n_ids, windows * h), the distinct ids it can meet
+__host__ __device__ inline uint32_t mibf_classify_cap(uint64_t bytes, uint32_t k, uint32_t h, uint64_t n_ids)
+{
+	const uint64_t frames = bytes >= k ? bytes - k + 1 : 0;
+	uint64_t bound = frames * h;
+	bound = bound < n_ids ? bound : n_ids;
+	uint32_t cap = 16;
+	while (cap <= bound && cap < 0x80000000u)
+		cap <<= 1;
+	return cap;
+}
+struct MibfClassifyArgs {
+	const void* values;          // T[len * h] of the batch (MIBF_QUERY)
+	const uint64_t* valid_bits;  // clean windows = frames
+	const uint64_t* match_bits;  // frames that hit
+	const uint8_t* hit_masks;    // spaced seeds: m_hits per window
+	LayoutParams layout;         // of the batch
+	uint32_t h, k, spaced;
+	uint32_t extra_frame_limit, min_count, best_hit_agree, max_results;
+	double extra_count;
+	const double* per_frame_prob;     // [n_ids]
+	const uint32_t* min_count_per_id; // [n_ids]
+	uint64_t n_ids;
+	void* hits;                       // btlbf_mibf_hit[(row0 + n_seqs) * max_results]
+	uint32_t *n_hits, *sat_count, *eval_count;
+	uint64_t row0;                    // result row of the batch's first sequence
+	const uint32_t* big_list;         // sequences of the batch whose table does not fit LDS ...
+	const uint64_t* big_off;          // ... and where each one's table starts in big_tab (in slots)
+	uint32_t* big_tab;
+	uint64_t n_big;
+	unsigned long long* stat;         // optional: {sequences walked over an LDS table, over a global table} +=
+};
+hipError_t launch_mibf_classify(int id_bytes, const MibfClassifyArgs& a, hipStream_t s);
+hipError_t launch_mibf_classify_maxid(int id_bytes, const void* data, uint64_t n, unsigned long long* out, hipStream_t s);
 
 } // namespace btlbf

@@ -213,6 +213,8 @@ __global__ __launch_bounds__(kMThreads) void mibf_seq_kernel(const MibfArgs a)
 				if (!ok) {
 					for (uint32_t i = 0; i < h; ++i)
 						static_cast<T*>(a.values)[gp * h + i] = 0;
+					if (a.hit_masks)
+						a.hit_masks[gp] = 0;
 					return;
 				}
 				// atRank (MIBloomFilter.hpp:478-515) + getMatchSignature (MIBFQuerySupport.hpp:158-217)
@@ -237,6 +239,8 @@ __global__ __launch_bounds__(kMThreads) void mibf_seq_kernel(const MibfArgs a)
 				for (uint32_t i = 0; i < kMibfMaxHash; ++i)
 					if (i < h)
 						static_cast<T*>(a.values)[gp * h + i] = vals[i];
+				if (a.hit_masks)
+					a.hit_masks[gp] = match ? (uint8_t)hits : (uint8_t)0;
 				hit_mask |= (uint32_t)match << w;
 				c1 += match;
 			}

@@ -642,6 +642,17 @@ def fastx_batches(path, k, per_line=False, batch_bytes=0, pageable=True, byte_ra
         L.btlbf_fastx_close(r)
 
 
+# btlbf_mibf_hit
+HIT_DTYPE = np.dtype([("id", "<u4"), ("count", "<u2"), ("nonSatCount", "<u2"), ("totalCount", "<u2"),
+                      ("totalNonSatCount", "<u2"), ("nonSatFrameCount", "<u2"), ("solidCount", "<u2")])
+
+
+def hits_from_words(words):
+    """[..., 4] 32-bit words of btlbf_mibf_hit records (host) -> structured array [...] of HIT_DTYPE"""
+    w = np.ascontiguousarray(np.asarray(words).astype(np.uint32, copy=False))
+    return w.view(HIT_DTYPE).reshape(w.shape[:-1])
+
+
 class MIBloomFilter(_Owned):
     """Multi-index Bloom filter over a stage-1 bit filter (btlbf_mibf_*; MIBloomFilter.hpp, MIBFConstructSupport.hpp,
     MIBFQuerySupport.hpp): an ID array of uint16 (id_bytes=2) or uint32 (id_bytes=4) in HBM, addressed by
@@ -725,6 +736,49 @@ class MIBloomFilter(_Owned):
         check(self._L.btlbf_mibf_query_seqs(self._h, b.ptr, n, C.byref(lay) if lay else None, int(max_miss), p_vals,
                                             p_hit, p_valid, p_cnt, b.mem, _stream_ptr(stream, b.keep)))
         return (vals, hit, valid, cnt) if want_counts else (vals, hit, valid)
+
+    def classify(self, seqs, per_frame_prob, min_count, *, extra_count=1.0, extra_frame_limit=0, max_miss=0,
+                 min_frames=1, best_hit_agree=False, max_results=8, starts=None, read_len=0, stream=None):
+        """MIBFQuerySupport<T>::query(itr, minCount) (MIBFQuerySupport.hpp:95-109) of every sequence ->
+        (hits[n_seqs, max_results] (HIT_DTYPE), n_hits[n_seqs], sat_count[n_seqs], eval_count[n_seqs]).
+        per_frame_prob[id] and min_count[id] are the reference's perFrameProb and minCount vectors; extra_count,
+        extra_frame_limit, max_miss, min_frames (its minCount constructor argument) and best_hit_agree its constructor
+        arguments.  n_hits counts every significant result; the first max_results of them are in hits.  Device
+        input: the tables and results are torch tensors on that device (hits as int32[n_seqs, max_results, 4]:
+        hits_from_words decodes a host copy)."""
+        b = _Buf(seqs)
+        lay, keep = _layout(starts, read_len, b.mem)
+        if lay is None:
+            raise ValueError("classify needs starts or read_len")
+        n_seqs = lay.n_seqs if starts is not None else b.nbytes // read_len
+        n_ids = len(per_frame_prob)
+        if len(min_count) != n_ids:
+            raise ValueError("per_frame_prob and min_count must have one entry per id")
+        if b.mem == DEVICE:
+            import torch
+
+            prob = _Buf(torch.as_tensor(per_frame_prob, dtype=torch.float64, device=b.keep.device).contiguous())
+            minc = _Buf(torch.as_tensor(min_count, dtype=torch.int32, device=b.keep.device).contiguous())
+        else:
+            prob = _Buf(np.ascontiguousarray(per_frame_prob, np.float64), np.float64)
+            minc = _Buf(np.ascontiguousarray(min_count, np.uint32), np.uint32)
+        par = _lib.MibfClassifyParams(float(extra_count), int(extra_frame_limit), int(max_miss), int(min_frames),
+                                      int(bool(best_hit_agree)), int(max_results))
+        words, p_hits = _out(b, (n_seqs, max(int(max_results), 1), 4), np.uint32)
+        n_hits, p_n = _out(b, n_seqs, np.uint32)
+        sat, p_sat = _out(b, n_seqs, np.uint32)
+        ev, p_ev = _out(b, n_seqs, np.uint32)
+        check(self._L.btlbf_mibf_classify_seqs(self._h, b.ptr, b.nbytes, C.byref(lay), C.byref(par), prob.ptr, minc.ptr,
+                                               n_ids, p_hits, p_n, p_sat, p_ev, b.mem, _stream_ptr(stream, b.keep)))
+        if b.mem == DEVICE:
+            return words, n_hits, sat, ev
+        return hits_from_words(words), n_hits, sat, ev
+
+    def classifyPaths(self):
+        """(sequences walked with their table in LDS, in HBM) of the last classify call"""
+        out = (C.c_uint64 * 2)()
+        check(self._L.btlbf_mibf_classify_paths(self._h, out))
+        return int(out[0]), int(out[1])
 
     def decode(self, values):
         """raw T values -> (id, saturated) as the reference's pair (v & antiMask, v > mask)"""

@@ -368,6 +368,55 @@ int btlbf_mibf_download_counts(btlbf_mibf* m, void* host_dst);
 int btlbf_mibf_store(btlbf_mibf* m, const char* path);
 int btlbf_mibf_load(btlbf_mibf** out, const char* path, btlbf_filter* f, unsigned id_bytes);
 
+/* ---- read classification over the miBF (MIBFQuerySupport.hpp) ------------------------------------------
+ * mibf_classify_seqs : MIBFQuerySupport<T>::query(itr, minCount) (MIBFQuerySupport.hpp:95-109) of every sequence of the
+ *   buffer, each on its own and from fresh state (init, :419-428).  A layout is required.
+ *   Frames are the sequence's clean windows in position order (the valid bits of btlbf_mibf_query_seqs).  Without seeds
+ *   (ntHashIterator, :408-417) a frame hits when all h bits are set; evalCount gets +1 per frame (:415) and +1 per value
+ *   looked up (:437).  With seeds (stHashIterator, h2 = 1, :397-406) a frame hits with at most max_miss clear bits, only
+ *   the set positions are looked up, and misses is passed on.  A hit frame runs updatesCounts (:430-518) exactly: the raw /
+ *   masked seenSet rules, nonSatFrameCount and solidCount only in frames without a saturated value (solidCount only with
+ *   misses == 0), both candidate rules (:495-507), updateMaxCounts with its `else if` (:522-526), and the two extraFrame
+ *   statements (:509-516, extra_frame_limit < extraFrame++ with the post-increment).  The walk stops at the first frame
+ *   that returns true (:102-105).  The six counters are uint16_t and wrap; satCount and evalCount are 32-bit.  Then
+ *   summarizeCandiates (:555-595): the gate min_count <= best nonSatFrameCount, isValid, the sortCandidates order,
+ *   isRoughlyEqualOrLarger against the first, best_hit_agree.  A sequence without a frame gives the emptyResult: 0 hits,
+ *   satCount 0, evalCount 0.
+ *   hits[n_seqs * max_results]: n_hits[s] is the full number of significant results of sequence s; its first
+ *   min(n_hits[s], max_results) records are written in result order and the rest of its row is zero.  frameProb of a
+ *   record is per_frame_prob[id].  sat_count[s] / eval_count[s] = getSatCount() / getEvalCount() after the query.
+ *   hits, n_hits, sat_count, eval_count, per_frame_prob and min_count_per_id live in memory space mem.
+ *   This library's rules where the reference leaves a choice:
+ *   - sortCandidates is a strict order whenever two candidates' frameProb differ; full ties keep the order in which the
+ *     ids first entered the candidate list.
+ *   - the reference indexes m_counts, minCount and perFrameProb by id (v & ~mask when v > mask, else v itself, so an
+ *     entry equal to the mask indexes as the mask); an index >= n_ids is undefined behaviour there.  Here the call first
+ *     takes the largest index over the whole data array (a reduction, cached until the array next changes) and returns
+ *     EINVAL with nothing written unless it is below n_ids.  Id 0 (an empty entry) is counted like any other id.
+ *   - compareStdErr / compareStdErrLarger are evaluated in double with an IEEE square root and without contraction.  A
+ *     reference built with contraction may fuse a - sqrt(a) * extra_count; the results agree bit for bit when
+ *     extra_count is a power of two (0.5, 1, 2: the product is then exact), and only those values are pinned by tests.
+ *   - candidates present but none passing isValid (the reference then reads signifResults[0] of an empty vector): 0 hits.
+ *   - the paired overload query(itr1, itr2, minCount) (:111-130) is not provided.
+ *   Errors: a null pointer, max_results == 0, n_ids == 0 or n_ids > 2^(bits(T)-1): EINVAL before any HIP call.  Sequences
+ *   are classified in batches under the btlbf_mibf_set_scratch budget (per base h values, a hit mask and two bitmap bits;
+ *   a sequence that can meet more than 255 distinct ids also a table of its own in HBM); a single sequence that does not
+ *   fit returns ENOMEM with nothing written.
+ * mibf_classify_paths : out2 = {sequences walked with their table in LDS, in HBM} of the last classify call. */
+typedef struct {
+	uint32_t id;
+	uint16_t count, nonSatCount, totalCount, totalNonSatCount, nonSatFrameCount, solidCount;
+} btlbf_mibf_hit; /* 16 bytes */
+typedef struct {
+	double extra_count;
+	uint32_t extra_frame_limit, max_miss, min_count, best_hit_agree, max_results;
+} btlbf_mibf_classify_params;
+int btlbf_mibf_classify_seqs(btlbf_mibf* m, const char* seq, uint64_t len, const btlbf_layout* layout,
+                             const btlbf_mibf_classify_params* p, const double* per_frame_prob,
+                             const uint32_t* min_count_per_id, uint64_t n_ids, btlbf_mibf_hit* hits, uint32_t* n_hits,
+                             uint32_t* sat_count, uint32_t* eval_count, int mem, void* stream);
+int btlbf_mibf_classify_paths(btlbf_mibf* m, uint64_t* out2);
+
 /* ---- multi-GPU hash-range sharding ------------------------------------------------
  * The M-bit filter is cut into n_shards contiguous bit ranges; shard g (btlbf_create_shard) holds
  * positions [g*M/n, (g+1)*M/n).  Routing is by POSITION, so the concatenated shard bodies are the

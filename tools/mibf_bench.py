@@ -1,7 +1,8 @@
 """miBF throughput on the issue's shape: 10^7 synthetic 150-base reads (1.2*10^9 k-mers), C5 spaced seeds, k = 31, a
 stage-1 filter of calcOptimalSize(1.2e9 entries, fpr 0.5, 4 hashes) bits (a multiple of 64, not a power of two), ids =
 read index / 10^4 + 1 as uint16.  Prints one JSON line: Gk-mers/s and ms per call of insert-IDs, parallel saturation
-and query (max_miss 0 and 1), each timed once after the stage-1 build.
+query (max_miss 0 and 1) and read classification (early stop after 2 extra frames, and the full walk), each timed once
+after the stage-1 build.
     python tools/mibf_bench.py [n_reads] [scratch_GiB]
 (per-kernel times: run it under rocprofv3 --kernel-trace --stats)"""
 import json
@@ -58,6 +59,18 @@ def main():
         res["ms"]["query_mm%d" % mx] = round(t_q, 2)
         res["query_mm%d_matched" % mx] = int(out[3][1])
         del out
+    # classification of the same reads (MIBFQuerySupport::query per read): phase 1 is the query above, into scratch
+    n_ids = n_reads // 10_000 + 2
+    prob = torch.full((n_ids,), 1e-3, dtype=torch.float64, device="cuda")
+    minc = torch.ones(n_ids, dtype=torch.int32, device="cuda")
+    for lim in (2, 1 << 30):
+        t_c, out = timed(lambda: mi.classify(reads, prob, minc, extra_frame_limit=lim, max_results=4, read_len=L))
+        name = "classify_limit2" if lim == 2 else "classify_full_walk"
+        res["ms"][name] = round(t_c, 2)
+        res[name] = {"reads_per_s": round(n_reads / t_c * 1e3), "reads_with_hits": int((out[1] > 0).sum()),
+                     "tables_lds_global": list(mi.classifyPaths())}
+        del out
+    res["query_mm0_reads_per_s"] = round(n_reads / res["ms"]["query_mm0"] * 1e3)
     res["gkmers_per_s"] = {kk: round(kmers / v / 1e6, 3) for kk, v in res["ms"].items() if kk not in ("create",)}
     res["pop_nonzero"], res["pop_saturated"] = mi.getPopNonZero(), mi.getPopSaturated()
     print(json.dumps(res))
