@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <cerrno>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -15,15 +16,12 @@
 
 using namespace btlbf;
 
-// -------------------------------------------------------------------------------------------------
-// multi-index Bloom filter (miBF stages 2-4): the ID array over the rank structure (mibf_kernels.hip)
-// -------------------------------------------------------------------------------------------------
 struct btlbf_mibf {
 	std::mutex mu;
 	int device = 0;
 	unsigned id_bytes = 2, h = 0, k = 0;
 	uint64_t n_bits = 0, n_blocks = 0, pop = 0;
-	uint64_t budget = 0; // 0 = kMibfDefaultScratch
+	uint64_t budget = 0; // as set; mibf_budget() is what a call may use
 	ModParams mod{};
 	HashParams hp{};
 	std::vector<std::string> seeds;
@@ -32,7 +30,7 @@ struct btlbf_mibf {
 	void* d_counts = nullptr; // pop T
 	uint64_t* d_pos_tab = nullptr;
 	uint16_t* d_dc_idx = nullptr;
-	unsigned long long* d_stat = nullptr; // 8 x u64: [0..3] call counters, [4] classify's largest id, [5..6] its table paths
+	MibfStat* d_stat = nullptr;
 	// classify: the largest m_counts index over the data array, valid until the array next changes
 	bool max_id_known = false;
 	uint64_t max_id = 0;
@@ -40,9 +38,6 @@ struct btlbf_mibf {
 };
 
 namespace {
-
-constexpr uint64_t kMibfDefaultScratch = 2ull << 30;
-constexpr uint32_t kMibfMaxHashHost = 8;
 
 void mibf_free(btlbf_mibf* m)
 {
@@ -66,8 +61,8 @@ int mibf_make(btlbf_mibf** out, btlbf_filter* f, unsigned id_bytes, const std::v
 {
 	if (f->kind != BTLBF_BLOOM || f->shard_count != 1)
 		return fail(BTLBF_EINVAL, "miBF: needs a whole bit filter");
-	if (f->h == 0 || f->h > kMibfMaxHashHost)
-		return fail(BTLBF_EINVAL, "miBF: %u hash values per window (1..%u supported)", f->h, kMibfMaxHashHost);
+	if (f->h == 0 || f->h > kMibfMaxHash)
+		return fail(BTLBF_EINVAL, "miBF: %u hash values per window (1..%u supported)", f->h, kMibfMaxHash);
 	HashParams hp;
 	fill_hash_params(hp, f->k, f->h);
 	btlbf_mibf* m = new btlbf_mibf();
@@ -94,7 +89,7 @@ int mibf_make(btlbf_mibf** out, btlbf_filter* f, unsigned id_bytes, const std::v
 	m->hp = hp;
 	m->n_bits = f->size;
 	fill_mod(m->mod, f->size, 0, f->size);
-	hipError_t e = hipMalloc((void**)&m->d_stat, 64);
+	hipError_t e = hipMalloc((void**)&m->d_stat, sizeof(MibfStat));
 	if (e == hipSuccess)
 		e = rank_build(f, &m->d_il, &m->n_blocks, &m->pop);
 	if (e != hipSuccess && !m->d_il) {
@@ -130,15 +125,12 @@ int mibf_make(btlbf_mibf** out, btlbf_filter* f, unsigned id_bytes, const std::v
 	return BTLBF_OK;
 }
 
-// the sequences of one call: device buffer, a host copy of the sequence boundaries (batches are cut on them), ids
+// the sequences of one call: device buffer, the sequence boundaries on the host (batches are cut on them), ids
 struct MibfCall {
 	SeqView v;
 	DevBuf ids_buf;
 	const uint32_t* d_ids = nullptr;
-	uint64_t n_seqs = 0;
-	uint32_t L = 0;
-	std::vector<uint64_t> starts; // ragged layouts: n_seqs + 1 offsets
-	uint64_t start(uint64_t s) const { return L ? s * L : starts[s]; }
+	MibfSeqs q;
 };
 
 int mibf_prepare(MibfCall& c, const char* seq, uint64_t len, const btlbf_layout* layout, const uint32_t* ids, int mem,
@@ -151,46 +143,44 @@ int mibf_prepare(MibfCall& c, const char* seq, uint64_t len, const btlbf_layout*
 	int rc = make_view(c.v, seq, len, layout, mem, s);
 	if (rc)
 		return rc;
+	MibfSeqs& q = c.q;
 	if (layout->starts) {
-		c.n_seqs = layout->n_seqs;
-		c.starts.resize(c.n_seqs + 1);
+		q.n_seqs = layout->n_seqs;
+		q.starts.resize(q.n_seqs + 1);
 		if (mem == BTLBF_DEVICE)
-			HIP_TRY(hipMemcpy(c.starts.data(), layout->starts, (c.n_seqs + 1) * 8, hipMemcpyDeviceToHost));
+			HIP_TRY(hipMemcpy(q.starts.data(), layout->starts, (q.n_seqs + 1) * 8, hipMemcpyDeviceToHost));
 		else
-			memcpy(c.starts.data(), layout->starts, (c.n_seqs + 1) * 8);
-		if (c.starts[0] != 0 || c.starts[c.n_seqs] != len)
+			memcpy(q.starts.data(), layout->starts, (q.n_seqs + 1) * 8);
+		if (q.starts[0] != 0 || q.starts[q.n_seqs] != len)
 			return fail(BTLBF_EINVAL, "starts[0] must be 0 and starts[n_seqs] must equal len");
-		for (uint64_t i = 0; i < c.n_seqs; ++i)
-			if (c.starts[i + 1] < c.starts[i])
+		for (uint64_t i = 0; i < q.n_seqs; ++i)
+			if (q.starts[i + 1] < q.starts[i])
 				return fail(BTLBF_EINVAL, "starts must not decrease");
 	} else {
-		c.L = layout->read_len;
-		c.n_seqs = len / c.L;
+		q.read_len = layout->read_len;
+		q.n_seqs = len / q.read_len;
 	}
-	if (!want_ids)
-		return BTLBF_OK;
-	if (mem == BTLBF_DEVICE) {
-		c.d_ids = ids;
-	} else {
-		HIP_TRY(c.ids_buf.alloc((c.n_seqs + 1) * 4));
-		if (c.n_seqs)
-			HIP_TRY(hipMemcpyAsync(c.ids_buf.p, ids, c.n_seqs * 4, hipMemcpyHostToDevice, s));
+	c.d_ids = ids;
+	if (want_ids && mem != BTLBF_DEVICE) {
+		HIP_TRY(c.ids_buf.alloc((q.n_seqs + 1) * 4));
+		if (q.n_seqs)
+			HIP_TRY(hipMemcpyAsync(c.ids_buf.p, ids, q.n_seqs * 4, hipMemcpyHostToDevice, s));
 		c.d_ids = c.ids_buf.as<uint32_t>();
 	}
 	return BTLBF_OK;
 }
 
-// sequences [s0, s1) as a buffer of their own: the layout's starts rebased to the batch's first byte
-int mibf_batch_layout(const MibfCall& c, uint64_t s0, uint64_t s1, DevBuf& starts_buf, LayoutParams& lay, hipStream_t s)
+// the sequences of a batch as a buffer of their own: the layout's starts rebased to the batch's first byte
+int mibf_batch_layout(const MibfSeqs& q, const MibfBatch& b, DevBuf& starts_buf, LayoutParams& lay, hipStream_t s)
 {
 	lay.starts = nullptr;
-	lay.n_seqs = s1 - s0;
-	lay.read_len = c.L;
-	if (c.L)
+	lay.n_seqs = b.s1 - b.s0;
+	lay.read_len = q.read_len;
+	if (q.read_len)
 		return BTLBF_OK;
-	std::vector<uint64_t> rb(s1 - s0 + 1);
-	for (uint64_t i = s0; i <= s1; ++i)
-		rb[i - s0] = c.starts[i] - c.starts[s0];
+	std::vector<uint64_t> rb(b.s1 - b.s0 + 1);
+	for (uint64_t i = b.s0; i <= b.s1; ++i)
+		rb[i - b.s0] = q.starts[i] - q.starts[b.s0];
 	HIP_TRY(starts_buf.alloc(rb.size() * 8));
 	HIP_TRY(hipMemcpyAsync(starts_buf.p, rb.data(), rb.size() * 8, hipMemcpyHostToDevice, s));
 	HIP_TRY(hipStreamSynchronize(s)); // rb is freed on return
@@ -198,24 +188,16 @@ int mibf_batch_layout(const MibfCall& c, uint64_t s0, uint64_t s1, DevBuf& start
 	return BTLBF_OK;
 }
 
-// the last sequence of the batch that starts at s0 and holds at most max_bytes bytes (at least one sequence)
-uint64_t mibf_batch_end(const MibfCall& c, uint64_t s0, uint64_t max_bytes, bool* too_big)
+// a plan that failed: no batch has run, so the ID array, the counts and the caller's outputs are as they were
+int mibf_too_big(const MibfPlan& plan)
 {
-	uint64_t s1 = s0 + 1;
-	*too_big = c.start(s1) - c.start(s0) > max_bytes;
-	if (c.L) {
-		const uint64_t n = std::max<uint64_t>(1, max_bytes / c.L);
-		return std::min(c.n_seqs, s0 + n);
-	}
-	while (s1 < c.n_seqs && c.starts[s1 + 1] - c.starts[s0] <= max_bytes)
-		++s1;
-	return s1;
+	return fail(BTLBF_ENOMEM, "miBF: sequence %llu does not fit the scratch budget (btlbf_mibf_set_scratch); nothing was "
+	            "changed", (unsigned long long)plan.too_big);
 }
 
 MibfArgs mibf_args(const btlbf_mibf* m, const uint8_t* seq, uint64_t len, const LayoutParams& lay)
 {
-	MibfArgs a;
-	memset(&a, 0, sizeof a);
+	MibfArgs a{};
 	a.seq = seq;
 	a.len = len;
 	a.layout = lay;
@@ -228,15 +210,24 @@ MibfArgs mibf_args(const btlbf_mibf* m, const uint8_t* seq, uint64_t len, const 
 	return a;
 }
 
-unsigned bit_len(uint64_t x)
+constexpr size_t kMibfCallStat = offsetof(MibfStat, max_id);   // the four counters of a call
+constexpr size_t kMibfCallStat2 = offsetof(MibfStat, mutated); // the first two: what a query and mibf_stats report
+
+// a MIBF_QUERY launch's arguments: its outputs (hit_masks is optional) and the call counters
+MibfArgs mibf_query_args(const btlbf_mibf* m, const uint8_t* seq, uint64_t len, const LayoutParams& lay, unsigned max_miss,
+                         void* values, void* hit_bits, void* valid_bits, void* hit_masks)
 {
-	unsigned b = 0;
-	while (x) {
-		++b;
-		x >>= 1;
-	}
-	return b;
+	MibfArgs a = mibf_args(m, seq, len, lay);
+	a.max_miss = max_miss;
+	a.values = values;
+	a.hit_bits = static_cast<uint8_t*>(hit_bits);
+	a.valid_bits = static_cast<uint8_t*>(valid_bits);
+	a.hit_masks = static_cast<uint8_t*>(hit_masks);
+	a.stat = &m->d_stat->clean;
+	return a;
 }
+
+unsigned bit_len(uint64_t x) { return x ? 64 - __builtin_clzll(x) : 0; }
 
 #pragma pack(push, 1)
 struct MibfFileHeader { // MIBloomFilter.hpp:106-117
@@ -305,23 +296,13 @@ extern "C" int btlbf_mibf_insert_ids_seqs(btlbf_mibf* m, const char* seq, uint64
 	int rc = mibf_prepare(c, seq, len, layout, ids, mem, s);
 	if (rc)
 		return rc;
-	if (len == 0 || c.n_seqs == 0)
+	if (len == 0 || c.q.n_seqs == 0)
 		return BTLBF_OK;
+	const MibfPlan plan = mibf_plan_insert(c.q, mibf_budget(m->budget), m->h);
+	if (!plan.ok())
+		return mibf_too_big(plan);
 	m->max_id_known = false;
-	// one batch: 4 x 8 bytes per hash value (keys, values, and the sort's output) + the sort's scratch
-	const uint64_t budget = m->budget ? m->budget : kMibfDefaultScratch;
-	const uint64_t max_bytes = std::max<uint64_t>(1, budget / (40ull * m->h));
-	uint64_t cap_bytes = 0;
-	for (uint64_t s0 = 0; s0 < c.n_seqs;) {
-		bool big;
-		const uint64_t s1 = mibf_batch_end(c, s0, max_bytes, &big);
-		if (big)
-			return fail(BTLBF_ENOMEM, "miBF: sequence %llu does not fit the scratch budget (btlbf_mibf_set_scratch)",
-			            (unsigned long long)s0);
-		cap_bytes = std::max(cap_bytes, c.start(s1) - c.start(s0));
-		s0 = s1;
-	}
-	const uint64_t cap = cap_bytes * m->h;
+	const uint64_t cap = plan.max_bytes * m->h;
 	size_t temp_bytes = 0;
 	HIP_TRY(mibf_sort_temp_bytes(cap, &temp_bytes));
 	DevBuf kin, vin, kout, vout, temp;
@@ -329,28 +310,25 @@ extern "C" int btlbf_mibf_insert_ids_seqs(btlbf_mibf* m, const char* seq, uint64
 		(void)hipGetLastError();
 		return fail(BTLBF_ENOMEM, "miBF: %llu bytes of insert scratch", (unsigned long long)(cap * 32 + temp_bytes));
 	}
-	for (uint64_t s0 = 0; s0 < c.n_seqs;) {
-		bool big;
-		const uint64_t s1 = mibf_batch_end(c, s0, max_bytes, &big);
-		const uint64_t b0 = c.start(s0), blen = c.start(s1) - b0, n = blen * m->h;
+	for (const MibfBatch& b : plan.batches) {
+		const uint64_t b0 = c.q.start(b.s0), blen = c.q.start(b.s1) - b0, n = blen * m->h;
 		DevBuf sb;
 		LayoutParams lay;
-		if ((rc = mibf_batch_layout(c, s0, s1, sb, lay, s)))
+		if ((rc = mibf_batch_layout(c.q, b, sb, lay, s)))
 			return rc;
 		MibfArgs a = mibf_args(m, c.v.d_seq + b0, blen, lay);
-		a.seq_bits = std::max(1u, bit_len(s1 - s0 - 1));
+		a.seq_bits = std::max(1u, bit_len(b.s1 - b.s0 - 1));
 		const unsigned end_bit = bit_len(m->pop) + a.seq_bits;
 		if (end_bit > 64)
 			return fail(BTLBF_EINVAL, "miBF: %llu sequences in one batch of a %llu-entry ID array",
-			            (unsigned long long)(s1 - s0), (unsigned long long)m->pop);
+			            (unsigned long long)(b.s1 - b.s0), (unsigned long long)m->pop);
 		a.keys = kin.as<uint64_t>();
 		a.vals = vin.as<uint64_t>();
-		HIP_TRY(launch_mibf_seq(0 /* MIBF_EMIT */, m->id_bytes, a, s));
+		HIP_TRY(launch_mibf_seq(MIBF_EMIT, m->id_bytes, a, s));
 		HIP_TRY(mibf_sort_pairs(temp.p, temp_bytes, kin.as<uint64_t>(), kout.as<uint64_t>(), vin.as<uint64_t>(),
 		                        vout.as<uint64_t>(), n, end_bit, s));
-		HIP_TRY(launch_mibf_insert_apply(m->id_bytes, kout.as<uint64_t>(), vout.as<uint64_t>(), n, a.seq_bits, c.d_ids, s0,
+		HIP_TRY(launch_mibf_insert_apply(m->id_bytes, kout.as<uint64_t>(), vout.as<uint64_t>(), n, a.seq_bits, c.d_ids, b.s0,
 		                                 m->d_data, m->d_counts, s));
-		s0 = s1;
 	}
 	HIP_TRY(hipStreamSynchronize(s)); // scratch is freed on return
 	return BTLBF_OK;
@@ -370,34 +348,27 @@ extern "C" int btlbf_mibf_saturate_seqs(btlbf_mibf* m, const char* seq, uint64_t
 	int rc = mibf_prepare(c, seq, len, layout, ids, mem, s);
 	if (rc)
 		return rc;
-	const uint64_t budget = m->budget ? m->budget : kMibfDefaultScratch;
+	const uint64_t budget = mibf_budget(m->budget);
 	m->max_id_known = false;
-	HIP_TRY(hipMemsetAsync(m->d_stat, 0, 32, s));
+	HIP_TRY(hipMemsetAsync(m->d_stat, 0, kMibfCallStat, s));
 	if (order == BTLBF_ORDER_SERIAL) {
 		// hash rows of a batch (8 bytes per hash value + the window bitmap), then one lane in buffer order
-		const uint64_t max_bytes = std::max<uint64_t>(1, budget / (8ull * m->h + 1));
+		const MibfPlan plan = mibf_plan_serial(c.q, budget, m->h);
+		if (!plan.ok())
+			return mibf_too_big(plan);
+		const uint64_t cap = plan.max_bytes + 64;
 		DevBuf rows, valid;
-		bool alloc = false;
-		for (uint64_t s0 = 0; s0 < c.n_seqs;) {
-			bool big;
-			const uint64_t s1 = mibf_batch_end(c, s0, max_bytes, &big);
-			if (big)
-				return fail(BTLBF_ENOMEM, "miBF: sequence %llu does not fit the scratch budget", (unsigned long long)s0);
-			const uint64_t b0 = c.start(s0), blen = c.start(s1) - b0;
-			if (!alloc) {
-				const uint64_t cap = std::min<uint64_t>(len, max_bytes) + 64;
-				if (rows.alloc(cap * 8 * m->h) || valid.alloc(bitmap_bytes(cap))) {
-					(void)hipGetLastError();
-					return fail(BTLBF_ENOMEM, "miBF: serial saturation scratch");
-				}
-				alloc = true;
-			}
+		if (rows.alloc(cap * 8 * m->h) || valid.alloc(bitmap_bytes(cap))) {
+			(void)hipGetLastError();
+			return fail(BTLBF_ENOMEM, "miBF: serial saturation scratch");
+		}
+		for (const MibfBatch& b : plan.batches) {
+			const uint64_t b0 = c.q.start(b.s0), blen = c.q.start(b.s1) - b0;
 			DevBuf sb;
 			LayoutParams lay;
-			if ((rc = mibf_batch_layout(c, s0, s1, sb, lay, s)))
+			if ((rc = mibf_batch_layout(c.q, b, sb, lay, s)))
 				return rc;
-			SeqArgs h;
-			memset(&h, 0, sizeof h);
+			SeqArgs h{};
 			h.seq = c.v.d_seq + b0;
 			h.len = blen;
 			h.layout = lay;
@@ -408,8 +379,7 @@ extern "C" int btlbf_mibf_saturate_seqs(btlbf_mibf* m, const char* seq, uint64_t
 			h.valid_bits = valid.as<uint8_t>();
 			HIP_TRY(launch_seq_op(OP_HASH_ONLY, h, s));
 			HIP_TRY(launch_mibf_serial_saturate(m->id_bytes, rows.as<uint64_t>(), valid.as<uint64_t>(), blen, m->h, m->mod,
-			                                    m->d_il, lay, c.d_ids, s0, m->d_data, m->d_counts, m->d_stat, s));
-			s0 = s1;
+			                                    m->d_il, lay, c.d_ids, b.s0, m->d_data, m->d_counts, &m->d_stat->clean, s));
 		}
 	} else if (len) {
 		// decisions against the snapshot: mutations (rank, window) 16 bytes + 16 more for their sort, saturated ranks 8
@@ -429,8 +399,8 @@ extern "C" int btlbf_mibf_saturate_seqs(btlbf_mibf* m, const char* seq, uint64_t
 		a.cap_mut = cap_mut;
 		a.cap_sat = cap_sat;
 		a.n_out = cnt.as<unsigned long long>();
-		a.stat = m->d_stat;
-		HIP_TRY(launch_mibf_seq(1 /* MIBF_DECIDE */, m->id_bytes, a, s));
+		a.stat = &m->d_stat->clean;
+		HIP_TRY(launch_mibf_seq(MIBF_DECIDE, m->id_bytes, a, s));
 		unsigned long long n_out[2];
 		HIP_TRY(hipMemcpyAsync(n_out, cnt.p, 16, hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipStreamSynchronize(s));
@@ -451,14 +421,14 @@ extern "C" int btlbf_mibf_saturate_seqs(btlbf_mibf* m, const char* seq, uint64_t
 		                                 c.d_ids, m->d_data, m->d_counts, s));
 		HIP_TRY(launch_mibf_saturate(m->id_bytes, sat.as<uint64_t>(), n_out[1], m->d_data, s));
 	}
-	uint64_t st[4];
-	HIP_TRY(hipMemcpyAsync(st, m->d_stat, 32, hipMemcpyDeviceToHost, s));
+	uint64_t st[kMibfCallStat / 8];
+	HIP_TRY(hipMemcpyAsync(st, m->d_stat, sizeof st, hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));
 	if (counts4) {
 		if (mem == BTLBF_DEVICE)
-			HIP_TRY(hipMemcpy(counts4, st, 32, hipMemcpyHostToDevice));
+			HIP_TRY(hipMemcpy(counts4, st, sizeof st, hipMemcpyHostToDevice));
 		else
-			memcpy(counts4, st, 32);
+			memcpy(counts4, st, sizeof st);
 	}
 	return BTLBF_OK;
 }
@@ -480,18 +450,13 @@ extern "C" int btlbf_mibf_query_seqs(btlbf_mibf* m, const char* seq, uint64_t le
 	if ((rc = o_val.prepare(values, len * m->h * m->id_bytes, mem, false, s)) ||
 	    (rc = o_hit.prepare(match_bits, bitmap_bytes(len), mem, false, s)) ||
 	    (rc = o_valid.prepare(valid_bits, bitmap_bytes(len), mem, false, s)) ||
-	    (rc = o_cnt.prepare(counts2, 16, mem, false, s)))
+	    (rc = o_cnt.prepare(counts2, kMibfCallStat2, mem, false, s)))
 		return rc;
-	HIP_TRY(hipMemsetAsync(m->d_stat, 0, 32, s));
-	MibfArgs a = mibf_args(m, v.d_seq, len, v.lay);
-	a.max_miss = max_miss;
-	a.values = o_val.d;
-	a.hit_bits = static_cast<uint8_t*>(o_hit.d);
-	a.valid_bits = static_cast<uint8_t*>(o_valid.d);
-	a.stat = m->d_stat;
-	HIP_TRY(launch_mibf_seq(2 /* MIBF_QUERY */, m->id_bytes, a, s));
+	HIP_TRY(hipMemsetAsync(m->d_stat, 0, kMibfCallStat, s));
+	HIP_TRY(launch_mibf_seq(MIBF_QUERY, m->id_bytes,
+	                        mibf_query_args(m, v.d_seq, len, v.lay, max_miss, o_val.d, o_hit.d, o_valid.d, nullptr), s));
 	if (o_cnt.d)
-		HIP_TRY(hipMemcpyAsync(o_cnt.d, m->d_stat, 16, hipMemcpyDeviceToDevice, s));
+		HIP_TRY(hipMemcpyAsync(o_cnt.d, m->d_stat, kMibfCallStat2, hipMemcpyDeviceToDevice, s));
 	if ((rc = o_val.finish(s)) || (rc = o_hit.finish(s)) || (rc = o_valid.finish(s)) || (rc = o_cnt.finish(s)))
 		return rc;
 	HIP_TRY(hipStreamSynchronize(s)); // d_stat is reused by the next call
@@ -521,14 +486,14 @@ extern "C" int btlbf_mibf_classify_seqs(btlbf_mibf* m, const char* seq, uint64_t
 	if (rc)
 		return rc;
 	m->cls_paths[0] = m->cls_paths[1] = 0;
-	if (c.n_seqs == 0)
+	if (c.q.n_seqs == 0)
 		return BTLBF_OK;
 	// every index the walk will use lies inside the caller's tables
 	if (!m->max_id_known) {
-		HIP_TRY(hipMemsetAsync(m->d_stat + 4, 0, 8, s));
-		HIP_TRY(launch_mibf_classify_maxid(m->id_bytes, m->d_data, m->pop, m->d_stat + 4, s));
+		HIP_TRY(hipMemsetAsync(&m->d_stat->max_id, 0, sizeof(MibfStat::max_id), s));
+		HIP_TRY(launch_mibf_classify_maxid(m->id_bytes, m->d_data, m->pop, &m->d_stat->max_id, s));
 		unsigned long long mx = 0;
-		HIP_TRY(hipMemcpyAsync(&mx, m->d_stat + 4, 8, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipMemcpyAsync(&mx, &m->d_stat->max_id, sizeof mx, hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipStreamSynchronize(s));
 		m->max_id = mx;
 		m->max_id_known = true;
@@ -536,48 +501,15 @@ extern "C" int btlbf_mibf_classify_seqs(btlbf_mibf* m, const char* seq, uint64_t
 	if (m->max_id >= n_ids)
 		return fail(BTLBF_EINVAL, "miBF classify: the ID array holds id %llu, the tables %llu entries; nothing was written",
 		            (unsigned long long)m->max_id, (unsigned long long)n_ids);
-	// batches: per byte h values, the hit mask and two bitmap bits; per sequence whose table does not fit LDS, the table
-	const uint64_t budget = m->budget ? m->budget : kMibfDefaultScratch;
-	const uint64_t per_byte = (uint64_t)m->h * m->id_bytes + 2;
-	struct Batch {
-		uint64_t s0, s1, big, slots;
-	};
-	std::vector<Batch> batches;
-	uint64_t cap_bytes = 0, cap_big = 0, cap_slots = 0;
-	auto seq_cost = [&](uint64_t i, uint64_t* slots) {
-		const uint64_t n = c.start(i + 1) - c.start(i);
-		const uint32_t cap = mibf_classify_cap(n, m->k, m->h, n_ids);
-		*slots = cap > kMibfClsLdsSlots ? cap : 0;
-		return n * per_byte + 64 + *slots * kMibfClsSlotWords * 4 + (*slots ? 12 : 0);
-	};
-	for (uint64_t s0 = 0; s0 < c.n_seqs;) {
-		Batch b{s0, s0, 0, 0};
-		uint64_t used = 0;
-		while (b.s1 < c.n_seqs && b.s1 - b.s0 < 0x7fffffffull) {
-			uint64_t slots;
-			const uint64_t cost = seq_cost(b.s1, &slots);
-			if (used + cost > budget)
-				break;
-			used += cost;
-			b.big += slots != 0;
-			b.slots += slots;
-			++b.s1;
-		}
-		if (b.s1 == b.s0)
-			return fail(BTLBF_ENOMEM, "miBF classify: sequence %llu does not fit the scratch budget (btlbf_mibf_set_scratch); "
-			            "nothing was written", (unsigned long long)s0);
-		cap_bytes = std::max(cap_bytes, c.start(b.s1) - c.start(b.s0));
-		cap_big = std::max(cap_big, b.big);
-		cap_slots = std::max(cap_slots, b.slots);
-		batches.push_back(b);
-		s0 = b.s1;
-	}
+	const MibfPlan plan = mibf_plan_classify(c.q, mibf_budget(m->budget), m->k, m->h, m->id_bytes, n_ids);
+	if (!plan.ok())
+		return mibf_too_big(plan);
 	DevBuf vals, hit, valid, masks, big_list, big_off, big_tab, tables;
-	if (vals.alloc(cap_bytes * m->h * m->id_bytes) || hit.alloc(bitmap_bytes(cap_bytes)) || valid.alloc(bitmap_bytes(cap_bytes)) ||
-	    masks.alloc(cap_bytes) || big_list.alloc(cap_big * 4) || big_off.alloc(cap_big * 8) ||
-	    big_tab.alloc(cap_slots * kMibfClsSlotWords * 4)) {
+	if (vals.alloc(plan.max_bytes * m->h * m->id_bytes) || hit.alloc(bitmap_bytes(plan.max_bytes)) ||
+	    valid.alloc(bitmap_bytes(plan.max_bytes)) || masks.alloc(plan.max_bytes) || big_list.alloc(plan.max_big * 4) ||
+	    big_off.alloc(plan.max_big * 8) || big_tab.alloc(plan.max_slots * kMibfClsSlotWords * 4)) {
 		(void)hipGetLastError();
-		return fail(BTLBF_ENOMEM, "miBF classify: scratch of %llu bytes", (unsigned long long)budget);
+		return fail(BTLBF_ENOMEM, "miBF classify: scratch of %llu bytes", (unsigned long long)mibf_budget(m->budget));
 	}
 	const double* d_prob = per_frame_prob;
 	const uint32_t* d_minc = min_count_per_id;
@@ -589,32 +521,23 @@ extern "C" int btlbf_mibf_classify_seqs(btlbf_mibf* m, const char* seq, uint64_t
 		d_minc = reinterpret_cast<const uint32_t*>(tables.as<uint8_t>() + n_ids * 8);
 	}
 	OutBuf o_hits, o_n, o_sat, o_eval;
-	if ((rc = o_hits.prepare(hits, c.n_seqs * p->max_results * sizeof(btlbf_mibf_hit), mem, true, s)) ||
-	    (rc = o_n.prepare(n_hits, c.n_seqs * 4, mem, true, s)) || (rc = o_sat.prepare(sat_count, c.n_seqs * 4, mem, true, s)) ||
-	    (rc = o_eval.prepare(eval_count, c.n_seqs * 4, mem, true, s)))
+	if ((rc = o_hits.prepare(hits, c.q.n_seqs * p->max_results * sizeof(btlbf_mibf_hit), mem, true, s)) ||
+	    (rc = o_n.prepare(n_hits, c.q.n_seqs * 4, mem, true, s)) || (rc = o_sat.prepare(sat_count, c.q.n_seqs * 4, mem, true, s)) ||
+	    (rc = o_eval.prepare(eval_count, c.q.n_seqs * 4, mem, true, s)))
 		return rc;
-	HIP_TRY(hipMemsetAsync(m->d_stat, 0, 32, s));
-	HIP_TRY(hipMemsetAsync(m->d_stat + 5, 0, 16, s));
-	std::vector<uint32_t> h_list;
-	std::vector<uint64_t> h_off;
-	for (const Batch& b : batches) {
-		const uint64_t b0 = c.start(b.s0), blen = c.start(b.s1) - b0;
+	HIP_TRY(hipMemsetAsync(m->d_stat, 0, kMibfCallStat, s));
+	HIP_TRY(hipMemsetAsync(m->d_stat->cls_paths, 0, sizeof(MibfStat::cls_paths), s));
+	uint64_t big0 = 0; // the batch's first entry of the plan's big lists
+	for (const MibfBatch& b : plan.batches) {
+		const uint64_t b0 = c.q.start(b.s0), blen = c.q.start(b.s1) - b0;
 		DevBuf sb;
 		LayoutParams lay;
-		if ((rc = mibf_batch_layout(c, b.s0, b.s1, sb, lay, s)))
+		if ((rc = mibf_batch_layout(c.q, b, sb, lay, s)))
 			return rc;
-		if (blen) {
-			MibfArgs a = mibf_args(m, c.v.d_seq + b0, blen, lay);
-			a.max_miss = p->max_miss;
-			a.values = vals.p;
-			a.hit_bits = hit.as<uint8_t>();
-			a.valid_bits = valid.as<uint8_t>();
-			a.hit_masks = masks.as<uint8_t>();
-			a.stat = m->d_stat;
-			HIP_TRY(launch_mibf_seq(2 /* MIBF_QUERY */, m->id_bytes, a, s));
-		}
-		MibfClassifyArgs q;
-		memset(&q, 0, sizeof q);
+		if (blen)
+			HIP_TRY(launch_mibf_seq(MIBF_QUERY, m->id_bytes,
+			                        mibf_query_args(m, c.v.d_seq + b0, blen, lay, p->max_miss, vals.p, hit.p, valid.p, masks.p), s));
+		MibfClassifyArgs q{};
 		q.values = vals.p;
 		q.valid_bits = valid.as<uint64_t>();
 		q.match_bits = hit.as<uint64_t>();
@@ -636,22 +559,12 @@ extern "C" int btlbf_mibf_classify_seqs(btlbf_mibf* m, const char* seq, uint64_t
 		q.sat_count = static_cast<uint32_t*>(o_sat.d);
 		q.eval_count = static_cast<uint32_t*>(o_eval.d);
 		q.row0 = b.s0;
-		q.stat = m->d_stat + 5;
+		q.stat = m->d_stat->cls_paths;
 		if (b.big) {
-			h_list.clear();
-			h_off.clear();
-			uint64_t off = 0;
-			for (uint64_t i = b.s0; i < b.s1; ++i) {
-				const uint32_t cap = mibf_classify_cap(c.start(i + 1) - c.start(i), m->k, m->h, n_ids);
-				if (cap > kMibfClsLdsSlots) {
-					h_list.push_back((uint32_t)(i - b.s0));
-					h_off.push_back(off);
-					off += cap;
-				}
-			}
-			HIP_TRY(hipMemcpyAsync(big_list.p, h_list.data(), h_list.size() * 4, hipMemcpyHostToDevice, s));
-			HIP_TRY(hipMemcpyAsync(big_off.p, h_off.data(), h_off.size() * 8, hipMemcpyHostToDevice, s));
-			HIP_TRY(hipStreamSynchronize(s)); // the two vectors are reused by the next batch
+			HIP_TRY(hipMemcpyAsync(big_list.p, &plan.big_seq[big0], b.big * 4, hipMemcpyHostToDevice, s));
+			HIP_TRY(hipMemcpyAsync(big_off.p, &plan.big_off[big0], b.big * 8, hipMemcpyHostToDevice, s));
+			HIP_TRY(hipStreamSynchronize(s)); // an early return frees the plan
+			big0 += b.big;
 			q.big_list = big_list.as<uint32_t>();
 			q.big_off = big_off.as<uint64_t>();
 			q.big_tab = big_tab.as<uint32_t>();
@@ -660,12 +573,11 @@ extern "C" int btlbf_mibf_classify_seqs(btlbf_mibf* m, const char* seq, uint64_t
 		HIP_TRY(launch_mibf_classify(m->id_bytes, q, s));
 	}
 	unsigned long long paths[2] = {0, 0};
-	HIP_TRY(hipMemcpyAsync(paths, m->d_stat + 5, 16, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(paths, m->d_stat->cls_paths, sizeof paths, hipMemcpyDeviceToHost, s));
 	if ((rc = o_hits.finish(s)) || (rc = o_n.finish(s)) || (rc = o_sat.finish(s)) || (rc = o_eval.finish(s)))
 		return rc;
 	HIP_TRY(hipStreamSynchronize(s)); // scratch is freed on return
-	m->cls_paths[0] = paths[0];
-	m->cls_paths[1] = paths[1];
+	memcpy(m->cls_paths, paths, sizeof paths);
 	return BTLBF_OK;
 }
 
@@ -674,8 +586,7 @@ extern "C" int btlbf_mibf_classify_paths(btlbf_mibf* m, uint64_t* out2)
 	if (!m || !out2)
 		return fail(BTLBF_EINVAL, "null argument");
 	std::lock_guard<std::mutex> lk(m->mu);
-	out2[0] = m->cls_paths[0];
-	out2[1] = m->cls_paths[1];
+	memcpy(out2, m->cls_paths, sizeof m->cls_paths);
 	return BTLBF_OK;
 }
 
@@ -685,10 +596,10 @@ extern "C" int btlbf_mibf_stats(btlbf_mibf* m, uint64_t* out3)
 		return fail(BTLBF_EINVAL, "null argument");
 	std::lock_guard<std::mutex> lk(m->mu);
 	DeviceGuard g(m->device);
-	HIP_TRY(hipMemset(m->d_stat, 0, 16));
-	HIP_TRY(launch_mibf_stats(m->id_bytes, m->d_data, m->pop, m->d_stat, nullptr));
+	HIP_TRY(hipMemset(m->d_stat, 0, kMibfCallStat2));
+	HIP_TRY(launch_mibf_stats(m->id_bytes, m->d_data, m->pop, &m->d_stat->clean, nullptr));
 	uint64_t st[2];
-	HIP_TRY(hipMemcpy(st, m->d_stat, 16, hipMemcpyDeviceToHost));
+	HIP_TRY(hipMemcpy(st, m->d_stat, kMibfCallStat2, hipMemcpyDeviceToHost));
 	out3[0] = m->pop;
 	out3[1] = st[0];
 	out3[2] = st[1];

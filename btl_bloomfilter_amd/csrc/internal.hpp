@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mibf_plan.hpp"
+
 namespace btlbf {
 
 // ntHash constants (values: /root/reference/vendor/nthash.hpp:183-193; the pre-rotated
@@ -324,7 +326,19 @@ struct MibfArgs {
 	unsigned long long* stat; // {clean, found | matched, mutated, saturated}
 	uint8_t* hit_masks;       // MIBF_QUERY, optional: per window, bit i = hash i found its bit set (m_hits) in a matched window
 };
-hipError_t launch_mibf_seq(int op, int id_bytes, const MibfArgs& a, hipStream_t s);
+enum MibfOp : int { MIBF_EMIT = 0, MIBF_DECIDE = 1, MIBF_QUERY = 2 };
+static constexpr uint32_t kMibfMaxHash = 8; // hash values per window the miBF kernels keep in registers
+// the device words of a miBF's counters; a kernel is handed a pointer to the first word it adds to
+struct MibfStat {
+	unsigned long long clean, found, mutated, saturated; // of one call; a query: {clean, matched}, mibf_stats: {non-zero, saturated}
+	unsigned long long max_id;                           // classify: the largest m_counts index over the data array
+	unsigned long long cls_paths[2];                     // classify: sequences walked over an LDS / a global table
+	unsigned long long spare;
+};
+// f(uint16_t{}) or f(uint32_t{}): the ID type T of a miBF with id_bytes 2 or 4
+template <class F>
+inline hipError_t mibf_by_id(int id_bytes, F&& f) { return id_bytes == 2 ? f(uint16_t{}) : f(uint32_t{}); }
+hipError_t launch_mibf_seq(MibfOp op, int id_bytes, const MibfArgs& a, hipStream_t s);
 hipError_t mibf_sort_temp_bytes(uint64_t n, size_t* bytes);
 hipError_t mibf_sort_pairs(void* temp, size_t temp_bytes, const uint64_t* k_in, uint64_t* k_out, const uint64_t* v_in,
                            uint64_t* v_out, uint64_t n, uint32_t end_bit, hipStream_t s);
@@ -342,21 +356,8 @@ hipError_t launch_mibf_hist(int id_bytes, const void* data, uint64_t n, uint64_t
                             hipStream_t s);
 
 // read classification over the miBF (mibf_classify_kernels.hip): MIBFQuerySupport<T>::query of every sequence of a batch
-// on the outputs of MIBF_QUERY.  A sequence's counts live in an open-addressed table of mibf_classify_cap() slots.
-static constexpr uint32_t kMibfClsMaxHash = 8;
-static constexpr uint32_t kMibfClsSlotWords = 6;  // uint32_t per table slot
-static constexpr uint32_t kMibfClsLdsSlots = 256; // tables up to this size are kept in LDS (6 KiB per wavefront)
-// slots for a sequence of `bytes` bytes: a power of two above min(n_ids, windows * h), the distinct ids it can meet
-__host__ __device__ inline uint32_t mibf_classify_cap(uint64_t bytes, uint32_t k, uint32_t h, uint64_t n_ids)
-{
-	const uint64_t frames = bytes >= k ? bytes - k + 1 : 0;
-	uint64_t bound = frames * h;
-	bound = bound < n_ids ? bound : n_ids;
-	uint32_t cap = 16;
-	while (cap <= bound && cap < 0x80000000u)
-		cap <<= 1;
-	return cap;
-}
+// on the outputs of MIBF_QUERY.  A sequence's counts live in an open-addressed table of mibf_classify_cap() slots
+// (mibf_plan.hpp, with the table constants: the host sizes its batches with them).
 struct MibfClassifyArgs {
 	const void* values;          // T[len * h] of the batch (MIBF_QUERY)
 	const uint64_t* valid_bits;  // clean windows = frames

@@ -19,7 +19,7 @@ static constexpr uint32_t kClsEmpty = 0xffffffffu;
 static constexpr uint32_t kClsWaves = 4; // sequences (wavefronts) per workgroup of the LDS kernel
 // a slot: {id, count | nonSatCount << 16, totalCount | totalNonSatCount << 16, nonSatFrameCount | solidCount << 16,
 // 1 + position in the candidate list (0: no candidate), slot of candidate number <this slot's index>}
-static constexpr uint32_t kW = kMibfClsSlotWords;
+static constexpr uint32_t kSlotWords = kMibfClsSlotWords;
 
 template <class T>
 struct ClsMask {
@@ -52,7 +52,7 @@ struct ClsCounts { // CountResult / QueryResult, widened
 
 __device__ __forceinline__ ClsCounts cls_load(const uint32_t* tab, uint32_t slot)
 {
-	const uint32_t w1 = tab[slot * kW + 1], w2 = tab[slot * kW + 2], w3 = tab[slot * kW + 3];
+	const uint32_t w1 = tab[slot * kSlotWords + 1], w2 = tab[slot * kSlotWords + 2], w3 = tab[slot * kSlotWords + 3];
 	return ClsCounts{w1 & 0xffffu, w1 >> 16, w2 & 0xffffu, w2 >> 16, w3 & 0xffffu, w3 >> 16};
 }
 
@@ -66,15 +66,15 @@ __device__ __forceinline__ uint32_t cls_slot(uint32_t* tab, uint32_t cap, uint32
 {
 	uint32_t s = ((id * 0x9E3779B1u) >> 7) & (cap - 1);
 	for (;;) {
-		const uint32_t key = tab[s * kW];
+		const uint32_t key = tab[s * kSlotWords];
 		if (key == id)
 			return s;
 		if (key == kClsEmpty) {
-			tab[s * kW] = id;
-			tab[s * kW + 1] = 0;
-			tab[s * kW + 2] = 0;
-			tab[s * kW + 3] = 0;
-			tab[s * kW + 4] = 0;
+			tab[s * kSlotWords] = id;
+			tab[s * kSlotWords + 1] = 0;
+			tab[s * kSlotWords + 2] = 0;
+			tab[s * kSlotWords + 3] = 0;
+			tab[s * kSlotWords + 4] = 0;
 			return s;
 		}
 		s = (s + 1) & (cap - 1);
@@ -131,9 +131,9 @@ __device__ __forceinline__ void cls_walk(const MibfClassifyArgs& a, uint32_t* ta
 		const uint64_t gp = cls_chunk_window(b, c) + lane;
 		bool ok = false, match = false;
 		uint32_t hm = 0;
-		uint32_t v[kMibfClsMaxHash];
+		uint32_t v[kMibfMaxHash];
 #pragma unroll
-		for (uint32_t i = 0; i < kMibfClsMaxHash; ++i)
+		for (uint32_t i = 0; i < kMibfMaxHash; ++i)
 			v[i] = 0;
 		if (gp < e) {
 			ok = (a.valid_bits[gp >> 6] >> (gp & 63)) & 1;
@@ -141,7 +141,7 @@ __device__ __forceinline__ void cls_walk(const MibfClassifyArgs& a, uint32_t* ta
 			if (match) {
 				hm = a.spaced ? a.hit_masks[gp] : (1u << h) - 1;
 #pragma unroll
-				for (uint32_t i = 0; i < kMibfClsMaxHash; ++i)
+				for (uint32_t i = 0; i < kMibfMaxHash; ++i)
 					if (i < h)
 						v[i] = values[gp * h + i];
 			}
@@ -158,15 +158,15 @@ __device__ __forceinline__ void cls_walk(const MibfClassifyArgs& a, uint32_t* ta
 			// ---- updatesCounts (:430-518) ----
 			const uint32_t hits = __shfl(hm, src, 64);
 			const uint32_t misses = h - __popc(hits);
-			uint32_t fv[kMibfClsMaxHash], fslot[kMibfClsMaxHash];
+			uint32_t fv[kMibfMaxHash], fslot[kMibfMaxHash];
 #pragma unroll
-			for (uint32_t i = 0; i < kMibfClsMaxHash; ++i) {
+			for (uint32_t i = 0; i < kMibfMaxHash; ++i) {
 				fv[i] = __shfl(v[i], src, 64);
 				fslot[i] = 0;
 			}
 			uint32_t seen = 0, fsat = 0; // seen: bit i = position i pushed its raw value onto m_seenSet
 #pragma unroll
-			for (uint32_t i = 0; i < kMibfClsMaxHash; ++i) {
+			for (uint32_t i = 0; i < kMibfMaxHash; ++i) {
 				if (i >= h || !((hits >> i) & 1))
 					continue;
 				const uint32_t raw = fv[i];
@@ -176,63 +176,63 @@ __device__ __forceinline__ void cls_walk(const MibfClassifyArgs& a, uint32_t* ta
 				fsat += sat;
 				const uint32_t s = cls_slot(tab, cap, id);
 				fslot[i] = s;
-				uint32_t w2 = inc_lo(tab[s * kW + 2]);
+				uint32_t w2 = inc_lo(tab[s * kSlotWords + 2]);
 				if (!sat)
 					w2 = inc_hi(w2);
-				tab[s * kW + 2] = w2;
+				tab[s * kSlotWords + 2] = w2;
 				bool raw_seen = false, id_seen = false;
 #pragma unroll
-				for (uint32_t j = 0; j < kMibfClsMaxHash; ++j) {
+				for (uint32_t j = 0; j < kMibfMaxHash; ++j) {
 					if (j < i && ((seen >> j) & 1)) {
 						raw_seen |= fv[j] == raw;
 						id_seen |= fv[j] == id;
 					}
 				}
 				if (!raw_seen) {
-					uint32_t w1 = tab[s * kW + 1];
+					uint32_t w1 = tab[s * kSlotWords + 1];
 					if (sat) {
 						if (!id_seen)
 							w1 = inc_lo(w1);
 					} else {
 						w1 = inc_lo(inc_hi(w1));
 					}
-					tab[s * kW + 1] = w1;
+					tab[s * kSlotWords + 1] = w1;
 					seen |= 1u << i;
 				}
 			}
 			if (fsat == 0) {
 #pragma unroll
-				for (uint32_t i = 0; i < kMibfClsMaxHash; ++i) {
+				for (uint32_t i = 0; i < kMibfMaxHash; ++i) {
 					if (!((seen >> i) & 1))
 						continue;
-					uint32_t w3 = inc_lo(tab[fslot[i] * kW + 3]);
+					uint32_t w3 = inc_lo(tab[fslot[i] * kSlotWords + 3]);
 					if (misses == 0)
 						w3 = inc_hi(w3);
-					tab[fslot[i] * kW + 3] = w3;
+					tab[fslot[i] * kSlotWords + 3] = w3;
 				}
 			} else {
 				++sat_count;
 			}
 #pragma unroll
-			for (uint32_t i = 0; i < kMibfClsMaxHash; ++i) {
+			for (uint32_t i = 0; i < kMibfMaxHash; ++i) {
 				if (!((seen >> i) & 1))
 					continue;
 				const uint32_t raw = fv[i];
 				if (raw > mask) {
 					bool plain = false; // the non-saturated version is in the set too
 #pragma unroll
-					for (uint32_t j = 0; j < kMibfClsMaxHash; ++j)
+					for (uint32_t j = 0; j < kMibfMaxHash; ++j)
 						plain |= j != i && ((seen >> j) & 1) && fv[j] == (raw & anti);
 					if (plain)
 						continue;
 				}
 				const uint32_t s = fslot[i];
-				const uint32_t id = tab[s * kW];
+				const uint32_t id = tab[s * kSlotWords];
 				const ClsCounts cr = cls_load(tab, s);
 				if (cr.count >= a.min_count_per_id[id] || (n_cand && cr.count >= b_count)) {
-					if (tab[s * kW + 4] == 0) {
-						tab[n_cand * kW + 5] = s;
-						tab[s * kW + 4] = ++n_cand;
+					if (tab[s * kSlotWords + 4] == 0) {
+						tab[n_cand * kSlotWords + 5] = s;
+						tab[s * kSlotWords + 4] = ++n_cand;
 					}
 					// updateMaxCounts (:520-542)
 					if (cr.nsFrame > b_nsf)
@@ -260,37 +260,37 @@ __device__ __forceinline__ void cls_walk(const MibfClassifyArgs& a, uint32_t* ta
 	if (n_cand && a.min_count <= b_nsf) {
 		uint32_t nv = 0;
 		for (uint32_t c = 0; c < n_cand; ++c) {
-			const uint32_t s = tab[c * kW + 5];
+			const uint32_t s = tab[c * kSlotWords + 5];
 			const ClsCounts r = cls_load(tab, s);
 			// isValid (:333-342)
 			if (cls_stderr(b_count, r.count) || cls_stderr(b_totalns, r.totalNonSat) || cls_stderr(b_nsf, r.nsFrame) ||
 			    cls_stderr(b_solid, r.solid) || cls_stderr(b_nonsat, r.nonSat) || cls_stderr(b_total, r.total)) {
-				tab[nv * kW + 5] = s;
+				tab[nv * kSlotWords + 5] = s;
 				++nv;
 			}
 		}
 		if (nv > 1) {
 			// sort(signifResults, sortCandidates) as an insertion sort: full ties keep the candidate-list order
 			for (uint32_t i = 1; i < nv; ++i) {
-				const uint32_t s = tab[i * kW + 5];
+				const uint32_t s = tab[i * kSlotWords + 5];
 				const ClsCounts x = cls_load(tab, s);
-				const double px = a.per_frame_prob[tab[s * kW]];
+				const double px = a.per_frame_prob[tab[s * kSlotWords]];
 				uint32_t j = i;
 				while (j > 0) {
-					const uint32_t sj = tab[(j - 1) * kW + 5];
-					if (!cls_before(x, px, cls_load(tab, sj), a.per_frame_prob[tab[sj * kW]]))
+					const uint32_t sj = tab[(j - 1) * kSlotWords + 5];
+					if (!cls_before(x, px, cls_load(tab, sj), a.per_frame_prob[tab[sj * kSlotWords]]))
 						break;
-					tab[j * kW + 5] = sj;
+					tab[j * kSlotWords + 5] = sj;
 					--j;
 				}
-				tab[j * kW + 5] = s;
+				tab[j * kSlotWords + 5] = s;
 			}
 			const ClsCounts f = cls_load(tab, tab[5]);
 			ClsCounts r0 = f, r1 = f;
 			for (int pass = 0; pass < 2; ++pass) {
 				uint32_t n = 0;
 				for (uint32_t i = 0; i < nv; ++i) {
-					const uint32_t s = tab[i * kW + 5];
+					const uint32_t s = tab[i * kSlotWords + 5];
 					const ClsCounts r = cls_load(tab, s);
 					// isRoughlyEqualOrLarger(signifResults[0], candidate) (:347-356)
 					if (!(cls_stderr_larger(f.count, r.count, a.extra_count) &&
@@ -306,7 +306,7 @@ __device__ __forceinline__ void cls_walk(const MibfClassifyArgs& a, uint32_t* ta
 						if (n == 1)
 							r1 = r;
 					} else if (n < a.max_results && lane == 0) {
-						cls_write_hit<T>(a, row, n, tab[s * kW], r);
+						cls_write_hit<T>(a, row, n, tab[s * kSlotWords], r);
 					}
 					++n;
 				}
@@ -322,7 +322,7 @@ __device__ __forceinline__ void cls_walk(const MibfClassifyArgs& a, uint32_t* ta
 		} else if (nv == 1) {
 			const uint32_t s = tab[5];
 			if (lane == 0)
-				cls_write_hit<T>(a, row, 0, tab[s * kW], cls_load(tab, s));
+				cls_write_hit<T>(a, row, 0, tab[s * kSlotWords], cls_load(tab, s));
 			n_res = 1;
 		}
 	}
@@ -349,7 +349,7 @@ __device__ __forceinline__ void cls_bounds(const MibfClassifyArgs& a, uint64_t s
 template <class T, int GLOBAL>
 __global__ __launch_bounds__(GLOBAL ? 64 : 64 * kClsWaves) void mibf_classify_kernel(const MibfClassifyArgs a)
 {
-	__shared__ uint32_t lds[GLOBAL ? 1 : kClsWaves][GLOBAL ? 1 : kMibfClsLdsSlots * kW];
+	__shared__ uint32_t lds[GLOBAL ? 1 : kClsWaves][GLOBAL ? 1 : kMibfClsLdsSlots * kSlotWords];
 	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
 	uint64_t s = GLOBAL ? 0 : (uint64_t)blockIdx.x * kClsWaves + wave;
 	bool mine = GLOBAL ? true : s < a.layout.n_seqs;
@@ -362,10 +362,10 @@ __global__ __launch_bounds__(GLOBAL ? 64 : 64 * kClsWaves) void mibf_classify_ke
 		cap = mibf_classify_cap(e - b, a.k, a.h, a.n_ids);
 		mine = GLOBAL ? true : cap <= kMibfClsLdsSlots;
 	}
-	uint32_t* tab = GLOBAL ? a.big_tab + a.big_off[blockIdx.x] * kW : lds[wave];
+	uint32_t* tab = GLOBAL ? a.big_tab + a.big_off[blockIdx.x] * kSlotWords : lds[wave];
 	if (mine)
 		for (uint32_t i = lane; i < cap; i += 64)
-			tab[i * kW] = kClsEmpty;
+			tab[i * kSlotWords] = kClsEmpty;
 	__syncthreads(); // the cleared keys are visible to every lane of the wave (no wave has left yet)
 	if (!mine)
 		return;
@@ -399,42 +399,34 @@ hipError_t launch_mibf_classify(int id_bytes, const MibfClassifyArgs& a, hipStre
 {
 	if (a.layout.n_seqs == 0)
 		return hipSuccess;
-	if (a.h == 0 || a.h > kMibfClsMaxHash)
-		return hipErrorInvalidValue;
 	const uint64_t blocks = (a.layout.n_seqs + kClsWaves - 1) / kClsWaves;
-	if (blocks > 0x7fffffffull || a.n_big > 0x7fffffffull)
+	if (a.h == 0 || a.h > kMibfMaxHash || blocks > 0x7fffffffull || a.n_big > 0x7fffffffull)
 		return hipErrorInvalidValue;
-	if (a.n_big < a.layout.n_seqs) {
-		if (id_bytes == 2)
-			hipLaunchKernelGGL((mibf_classify_kernel<uint16_t, 0>), dim3((unsigned)blocks), dim3(64 * kClsWaves), 0, s, a);
-		else
-			hipLaunchKernelGGL((mibf_classify_kernel<uint32_t, 0>), dim3((unsigned)blocks), dim3(64 * kClsWaves), 0, s, a);
-		hipError_t e = hipGetLastError();
-		if (e != hipSuccess)
-			return e;
-	}
-	if (a.n_big) {
-		if (id_bytes == 2)
-			hipLaunchKernelGGL((mibf_classify_kernel<uint16_t, 1>), dim3((unsigned)a.n_big), dim3(64), 0, s, a);
-		else
-			hipLaunchKernelGGL((mibf_classify_kernel<uint32_t, 1>), dim3((unsigned)a.n_big), dim3(64), 0, s, a);
-	}
-	return hipGetLastError();
+	return mibf_by_id(id_bytes, [&](auto t) {
+		using T = decltype(t);
+		if (a.n_big < a.layout.n_seqs) {
+			hipLaunchKernelGGL((mibf_classify_kernel<T, 0>), dim3((unsigned)blocks), dim3(64 * kClsWaves), 0, s, a);
+			hipError_t e = hipGetLastError();
+			if (e != hipSuccess)
+				return e;
+		}
+		if (a.n_big)
+			hipLaunchKernelGGL((mibf_classify_kernel<T, 1>), dim3((unsigned)a.n_big), dim3(64), 0, s, a);
+		return hipGetLastError();
+	});
 }
 
 hipError_t launch_mibf_classify_maxid(int id_bytes, const void* data, uint64_t n, unsigned long long* out, hipStream_t s)
 {
 	if (n == 0)
 		return hipSuccess;
-	uint64_t g = (n + 255) / 256;
-	g = g > 4096 ? 4096 : g;
-	if (id_bytes == 2)
-		hipLaunchKernelGGL(mibf_classify_maxid_kernel<uint16_t>, dim3((unsigned)g), dim3(256), 0, s,
-		                   static_cast<const uint16_t*>(data), n, out);
-	else
-		hipLaunchKernelGGL(mibf_classify_maxid_kernel<uint32_t>, dim3((unsigned)g), dim3(256), 0, s,
-		                   static_cast<const uint32_t*>(data), n, out);
-	return hipGetLastError();
+	const uint64_t g = std::min<uint64_t>((n + 255) / 256, 4096);
+	return mibf_by_id(id_bytes, [&](auto t) {
+		using T = decltype(t);
+		hipLaunchKernelGGL(mibf_classify_maxid_kernel<T>, dim3((unsigned)g), dim3(256), 0, s, static_cast<const T*>(data), n,
+		                   out);
+		return hipGetLastError();
+	});
 }
 
 } // namespace btlbf

@@ -27,7 +27,6 @@ namespace btlbf {
 
 static constexpr int kMThreads = 256;
 static constexpr int kMTile = kMThreads * kW;
-static constexpr uint32_t kMibfMaxHash = 8; // hash values per window the miBF kernels keep in registers
 
 // rank(p) = set bits before position p over the interleaved records (aux_kernels.hip rank_query_kernel); bit = bit p
 __device__ __forceinline__ uint64_t mibf_rank(const uint64_t* il, uint64_t p, uint32_t& bit)
@@ -83,8 +82,6 @@ __device__ __forceinline__ T mibf_set_data(T old, T id)
 {
 	return old > MibfMask<T>::mask ? (T)(id | MibfMask<T>::mask) : id;
 }
-
-enum MibfOp : int { MIBF_EMIT = 0, MIBF_DECIDE = 1, MIBF_QUERY = 2 };
 
 // hash % size (a uniform branch: the miBF kernels are not instantiated per modulus kind)
 __device__ __forceinline__ uint64_t mibf_reduce(uint64_t v, const ModParams& m)
@@ -467,14 +464,7 @@ __global__ __launch_bounds__(256) void mibf_hist_kernel(const T* data, uint64_t 
 
 // ---- launchers ---------------------------------------------------------------------------------------------------
 
-static uint64_t grid_for(uint64_t n, uint64_t cap = 65536)
-{
-	uint64_t g = (n + 255) / 256;
-	return g == 0 ? 1 : (g > cap ? cap : g);
-}
-
-template <class T>
-static hipError_t launch_mibf_seq_t(int op, const MibfArgs& a_in, hipStream_t s)
+hipError_t launch_mibf_seq(MibfOp op, int id_bytes, const MibfArgs& a_in, hipStream_t s)
 {
 	MibfArgs a = a_in;
 	if (a.len == 0)
@@ -502,8 +492,9 @@ static hipError_t launch_mibf_seq_t(int op, const MibfArgs& a_in, hipStream_t s)
 		hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kMThreads), dyn, s, a);
 		return hipGetLastError();
 	};
-	auto by_hs = [&](auto op_c) -> hipError_t {
+	auto by_hs = [&](auto op_c, auto t) -> hipError_t {
 		constexpr int OP = decltype(op_c)::value;
+		using T = decltype(t);
 		switch (hs) {
 		case 0: return go(mibf_seq_kernel<OP, 0, T>);
 		case 1: return go(mibf_seq_kernel<OP, 1, T>);
@@ -517,17 +508,14 @@ static hipError_t launch_mibf_seq_t(int op, const MibfArgs& a_in, hipStream_t s)
 		default: return hipErrorInvalidValue;
 		}
 	};
-	switch (op) {
-	case MIBF_EMIT: return by_hs(std::integral_constant<int, MIBF_EMIT>());
-	case MIBF_DECIDE: return by_hs(std::integral_constant<int, MIBF_DECIDE>());
-	case MIBF_QUERY: return by_hs(std::integral_constant<int, MIBF_QUERY>());
-	default: return hipErrorInvalidValue;
-	}
-}
-
-hipError_t launch_mibf_seq(int op, int id_bytes, const MibfArgs& a, hipStream_t s)
-{
-	return id_bytes == 2 ? launch_mibf_seq_t<uint16_t>(op, a, s) : launch_mibf_seq_t<uint32_t>(op, a, s);
+	return mibf_by_id(id_bytes, [&](auto t) {
+		switch (op) {
+		case MIBF_EMIT: return by_hs(std::integral_constant<int, MIBF_EMIT>(), t);
+		case MIBF_DECIDE: return by_hs(std::integral_constant<int, MIBF_DECIDE>(), t);
+		case MIBF_QUERY: return by_hs(std::integral_constant<int, MIBF_QUERY>(), t);
+		default: return hipErrorInvalidValue;
+		}
+	});
 }
 
 // sort scratch of rocPRIM's radix sort for n 64-bit key / 64-bit value pairs
@@ -546,46 +534,41 @@ hipError_t mibf_sort_pairs(void* temp, size_t temp_bytes, const uint64_t* k_in, 
 	return rocprim::radix_sort_pairs(temp, temp_bytes, k_in, k_out, v_in, v_out, (size_t)n, 0, end_bit, s);
 }
 
-hipError_t launch_mibf_insert_apply(int id_bytes, const uint64_t* keys, uint64_t* vals, uint64_t n, uint32_t seq_bits,
-                                    const uint32_t* ids, uint64_t seq0, void* data, void* counts, hipStream_t s)
+// a grid-stride kernel over n items: at most max_grid workgroups of 256 lanes
+template <class K, class... A>
+static hipError_t launch_over(uint64_t n, uint64_t max_grid, hipStream_t s, K kernel, A... args)
 {
 	if (n == 0)
 		return hipSuccess;
-	const dim3 g((unsigned)grid_for(n));
-	if (id_bytes == 2)
-		hipLaunchKernelGGL(mibf_insert_apply_kernel<uint16_t>, g, dim3(256), 0, s, keys, vals, n, seq_bits, ids, seq0,
-		                   static_cast<uint16_t*>(data), static_cast<uint16_t*>(counts));
-	else
-		hipLaunchKernelGGL(mibf_insert_apply_kernel<uint32_t>, g, dim3(256), 0, s, keys, vals, n, seq_bits, ids, seq0,
-		                   static_cast<uint32_t*>(data), static_cast<uint32_t*>(counts));
+	hipLaunchKernelGGL(kernel, dim3((unsigned)std::min((n + 255) / 256, max_grid)), dim3(256), 0, s, args...);
 	return hipGetLastError();
+}
+
+hipError_t launch_mibf_insert_apply(int id_bytes, const uint64_t* keys, uint64_t* vals, uint64_t n, uint32_t seq_bits,
+                                    const uint32_t* ids, uint64_t seq0, void* data, void* counts, hipStream_t s)
+{
+	return mibf_by_id(id_bytes, [&](auto t) {
+		using T = decltype(t);
+		return launch_over(n, 65536, s, mibf_insert_apply_kernel<T>, keys, vals, n, seq_bits, ids, seq0, static_cast<T*>(data),
+		                   static_cast<T*>(counts));
+	});
 }
 
 hipError_t launch_mibf_mutate_apply(int id_bytes, const uint64_t* keys, const uint64_t* vals, uint64_t n,
                                     const LayoutParams& lay, const uint32_t* ids, void* data, void* counts, hipStream_t s)
 {
-	if (n == 0)
-		return hipSuccess;
-	const dim3 g((unsigned)grid_for(n));
-	if (id_bytes == 2)
-		hipLaunchKernelGGL(mibf_mutate_apply_kernel<uint16_t>, g, dim3(256), 0, s, keys, vals, n, lay, ids,
-		                   static_cast<uint16_t*>(data), static_cast<uint16_t*>(counts));
-	else
-		hipLaunchKernelGGL(mibf_mutate_apply_kernel<uint32_t>, g, dim3(256), 0, s, keys, vals, n, lay, ids,
-		                   static_cast<uint32_t*>(data), static_cast<uint32_t*>(counts));
-	return hipGetLastError();
+	return mibf_by_id(id_bytes, [&](auto t) {
+		using T = decltype(t);
+		return launch_over(n, 65536, s, mibf_mutate_apply_kernel<T>, keys, vals, n, lay, ids, static_cast<T*>(data),
+		                   static_cast<T*>(counts));
+	});
 }
 
 hipError_t launch_mibf_saturate(int id_bytes, const uint64_t* ranks, uint64_t n, void* data, hipStream_t s)
 {
-	if (n == 0)
-		return hipSuccess;
-	const dim3 g((unsigned)grid_for(n));
-	if (id_bytes == 2)
-		hipLaunchKernelGGL(mibf_saturate_kernel<uint16_t>, g, dim3(256), 0, s, ranks, n, static_cast<uint32_t*>(data));
-	else
-		hipLaunchKernelGGL(mibf_saturate_kernel<uint32_t>, g, dim3(256), 0, s, ranks, n, static_cast<uint32_t*>(data));
-	return hipGetLastError();
+	return mibf_by_id(id_bytes, [&](auto t) {
+		return launch_over(n, 65536, s, mibf_saturate_kernel<decltype(t)>, ranks, n, static_cast<uint32_t*>(data));
+	});
 }
 
 hipError_t launch_mibf_serial_saturate(int id_bytes, const uint64_t* rows, const uint64_t* valid, uint64_t len, uint32_t h,
@@ -593,38 +576,31 @@ hipError_t launch_mibf_serial_saturate(int id_bytes, const uint64_t* rows, const
                                        const uint32_t* ids, uint64_t seq0, void* data, void* counts,
                                        unsigned long long* stat, hipStream_t s)
 {
-	if (id_bytes == 2)
-		hipLaunchKernelGGL(mibf_serial_saturate_kernel<uint16_t>, dim3(1), dim3(64), 0, s, rows, valid, len, h, mod, il,
-		                   lay, ids, seq0, static_cast<uint16_t*>(data), static_cast<uint16_t*>(counts), stat);
-	else
-		hipLaunchKernelGGL(mibf_serial_saturate_kernel<uint32_t>, dim3(1), dim3(64), 0, s, rows, valid, len, h, mod, il,
-		                   lay, ids, seq0, static_cast<uint32_t*>(data), static_cast<uint32_t*>(counts), stat);
-	return hipGetLastError();
+	return mibf_by_id(id_bytes, [&](auto t) {
+		using T = decltype(t);
+		hipLaunchKernelGGL(mibf_serial_saturate_kernel<T>, dim3(1), dim3(64), 0, s, rows, valid, len, h, mod, il, lay, ids,
+		                   seq0, static_cast<T*>(data), static_cast<T*>(counts), stat);
+		return hipGetLastError();
+	});
 }
 
 hipError_t launch_mibf_stats(int id_bytes, const void* data, uint64_t n, unsigned long long* out2, hipStream_t s)
 {
-	if (n == 0)
-		return hipSuccess;
-	const dim3 g((unsigned)grid_for(n, 4096));
-	if (id_bytes == 2)
-		hipLaunchKernelGGL(mibf_stats_kernel<uint16_t>, g, dim3(256), 0, s, static_cast<const uint16_t*>(data), n, out2);
-	else
-		hipLaunchKernelGGL(mibf_stats_kernel<uint32_t>, g, dim3(256), 0, s, static_cast<const uint32_t*>(data), n, out2);
-	return hipGetLastError();
+	return mibf_by_id(id_bytes, [&](auto t) {
+		using T = decltype(t);
+		return launch_over(n, 4096, s, mibf_stats_kernel<T>, static_cast<const T*>(data), n, out2);
+	});
 }
 
 hipError_t launch_mibf_hist(int id_bytes, const void* data, uint64_t n, uint64_t n_bins, unsigned long long* bins,
                             hipStream_t s)
 {
-	if (n == 0 || n_bins == 0)
+	if (n_bins == 0)
 		return hipSuccess;
-	const dim3 g((unsigned)grid_for(n, 2048));
-	if (id_bytes == 2)
-		hipLaunchKernelGGL(mibf_hist_kernel<uint16_t>, g, dim3(256), 0, s, static_cast<const uint16_t*>(data), n, n_bins, bins);
-	else
-		hipLaunchKernelGGL(mibf_hist_kernel<uint32_t>, g, dim3(256), 0, s, static_cast<const uint32_t*>(data), n, n_bins, bins);
-	return hipGetLastError();
+	return mibf_by_id(id_bytes, [&](auto t) {
+		using T = decltype(t);
+		return launch_over(n, 2048, s, mibf_hist_kernel<T>, static_cast<const T*>(data), n, n_bins, bins);
+	});
 }
 
 } // namespace btlbf

@@ -326,7 +326,9 @@ int btlbf_rank_query(const btlbf_rank* r, const uint64_t* values, uint64_t n, in
  *                   against data / counts as they stood at the start of the call; then each mutated position gets
  *                   counts += its choosers (T wrap) and the id of its last chooser in (sequence, window) order by
  *                   setData's rule against the start value; then every saturation is ORed in.  A parallel call whose
- *                   decisions do not fit the scratch budget returns ENOMEM and changes nothing.
+ *                   decisions do not fit the scratch budget returns ENOMEM and changes nothing.  A serial call walks
+ *                   the sequences in batches under the budget; one with a sequence that does not fit alone returns
+ *                   ENOMEM before any batch has run: data and counts are untouched then, too.
  *                   counts4 (optional, this memory space) = {clean windows, found, mutated, saturated}.
  *  mibf_query_seqs : getMatchSignature (MIBFQuerySupport.hpp:158-217) over atRank (MIBloomFilter.hpp:478-515):
  *                   values[len*h] (T, window p at row p): data[rank] at hit positions of a matching window, else 0;

@@ -174,6 +174,69 @@ def test_parallel_saturation_scratch_budget(bf):
     assert (m.data() == before).all() and (m.counts() == cb).all()
 
 
+def uniform_dense_case(bf):
+    """300 reads of 100 bases in the fixed read_len layout over 2^15 bits (dense, as dense_case)"""
+    rng = np.random.RandomState(29)
+    L, n = 100, 300
+    seq, _ = ragged(rng, n, L, L + 1, 0.005)
+    ids = rng.randint(1, 50, n)
+    f = stage1(bf, 1 << 15, 4, C5_SEEDS, seq, read_len=L)
+    ranks = mm.Ranks(f.download(), 1 << 15)
+    rows, valid = rows_of(bf, seq, 4, C5_SEEDS, read_len=L)
+    return seq, L, f, ranks, ids, rows.reshape(len(seq), 4), valid, mm.window_seqs(len(seq), None, L)
+
+
+@pytest.mark.parametrize("layout", ["ragged", "uniform"])
+@pytest.mark.parametrize("id_bytes", [2, 4])
+def test_serial_saturation_in_many_batches(bf, id_bytes, layout):
+    """the serial order under a scratch budget of 2^14 bytes: 496 bytes of sequence per batch (8 * 4 + 1 bytes of scratch
+    per byte), so about a hundred batches of the ragged reads and 75 batches of four 100-base reads; arrays and counters
+    as the model's single loop"""
+    if layout == "ragged":
+        seq, starts, f, ranks, ids, rows, valid, wseq = dense_case(bf, id_bytes, C5_SEEDS, 4)
+        L = 0
+    else:
+        seq, L, f, ranks, ids, rows, valid, wseq = uniform_dense_case(bf)
+        starts = None
+    m = bf.MIBloomFilter(f, id_bytes)
+    m.insertIDs(seq, ids, starts=starts, read_len=L)
+    data, counts = model_state(m)
+    mm.insert_ids(data, counts, ranks, rows, valid, wseq, ids, id_bytes)
+    assert (m.data().astype(np.int64) == data).all()
+    m.setScratchBudget(1 << 14)
+    got = m.insertSaturation(seq, ids, starts=starts, read_len=L, serial=True)
+    exp = mm.saturate_serial(data, counts, ranks, rows, valid, wseq, ids, id_bytes)
+    assert [got["clean"], got["found"], got["mutated"], got["saturated"]] == exp
+    assert exp[2] >= 0.01 * exp[0] and exp[3] >= 0.01 * exp[0] and exp[1] > 0  # all three outcomes
+    assert (m.counts().astype(np.int64) == counts).all()
+    assert (m.data().astype(np.int64) == data).all()
+
+
+@pytest.mark.parametrize("budget", [256, "between"])
+def test_serial_saturation_scratch_budget(bf, budget):
+    """a read that does not fit the budget alone: ENOMEM before any batch has run, the arrays untouched.  256 bytes hold
+    no read at all; the second budget holds the first reads and not a later, longer one"""
+    seq, starts, f, ranks, ids, rows, valid, wseq = dense_case(bf, 2, C5_SEEDS, 4)
+    from btl_bloomfilter_amd._lib import ENOMEM, BtlbfError
+
+    lens = np.diff(starts.astype(np.int64))
+    if budget == "between":
+        fit = max(int(lens[:3].max()), int(np.median(lens)))  # bytes of sequence per batch
+        assert lens.min() <= fit < lens.max() and (lens[:3] <= fit).all()
+        budget = fit * (8 * 4 + 1)
+    m = bf.MIBloomFilter(f, 2)
+    m.insertIDs(seq, ids, starts=starts)
+    before, cb = m.data(), m.counts()
+    m.setScratchBudget(budget)
+    with pytest.raises(BtlbfError) as e:
+        m.insertSaturation(seq, ids, starts=starts, serial=True)
+    assert e.value.code == ENOMEM
+    assert (m.data() == before).all() and (m.counts() == cb).all()
+    m.setScratchBudget(0)
+    m.insertSaturation(seq, ids, starts=starts, serial=True)  # ... and the call was not a no-op by accident
+    assert (m.data() != before).any()
+
+
 @pytest.mark.parametrize("seeds,h", CFG, ids=["C5", "nthash3"])
 @pytest.mark.parametrize("id_bytes", [2, 4])
 def test_query_against_model(bf, seeds, h, id_bytes):

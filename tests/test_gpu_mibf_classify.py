@@ -183,15 +183,45 @@ def test_max_results_truncates_records_not_the_count(bf):
     assert int(n[0]) >= 3 and hits.shape[1] == 1
 
 
-def test_long_sequence_takes_the_global_table(bf):
-    """about 5000 bases over about 300 ids: more distinct ids possible than an LDS table holds"""
+@pytest.fixture(scope="module")
+def long_case(bf):
+    """300 ids (301 table entries) and a contig of about 5000 bases over 50 of their genomes"""
     case = Case(bf, "C5", 2, 300, n_reads=0, bits=1 << 20, seed=9, length=100)
     rng = np.random.RandomState(3)
     contig = np.concatenate([ACGT[rng.randint(0, 4, 20)]] + genomes_of(np.random.RandomState(9), 300, 100)[:50])
+    return case, contig
+
+
+def test_long_sequence_takes_the_global_table(long_case):
+    """about 5000 bases over about 300 ids: more distinct ids possible than an LDS table holds"""
+    case, contig = long_case
     reads = [contig[:5000], contig[:80]]
     p = (1.0, LARGE, 1, 1, 0)
     check(case, reads, p, case.gpu(reads, p))
     assert case.m.classifyPaths() == (1, 1)
+
+
+def test_global_table_in_a_later_batch(long_case):
+    """three 80-base reads, then the 5000-base one, under a budget of 63000 bytes: the short reads cost 864 bytes each,
+    the long one 62364 with its 512-slot table, so it is a batch of its own behind theirs (tests/cpp/test_mibf_plan.cpp
+    asserts that plan for these lengths and this budget)"""
+    case, contig = long_case
+    reads = [contig[:80], contig[100:180], contig[200:280], contig[:5000]]
+    assert [len(s) for s in reads] == [80, 80, 80, 5000] and case.n_ids == 301 and case.h == 4 and case.id_bytes == 2
+    p = (1.0, LARGE, 1, 1, 0)
+    whole = case.gpu(reads, p)
+    check(case, reads, p, whole)
+    assert case.m.classifyPaths() == (3, 1)
+    case.m.setScratchBudget(63000)
+    try:
+        split = case.gpu(reads, p)
+        paths = case.m.classifyPaths()
+    finally:
+        case.m.setScratchBudget(0)
+    check(case, reads, p, split)
+    for a, b in zip(whole, split):
+        assert (np.asarray(a) == np.asarray(b)).all()
+    assert paths == (3, 1)
 
 
 def test_ids_beyond_the_tables_are_refused(cases, bf):
