@@ -66,7 +66,27 @@ enum {
 /* counting-filter update flavours (CountingBloomFilter.hpp:135-183) */
 enum { BTLBF_INCREMENT_MIN = 0, BTLBF_INCREMENT_ALL = 1 };
 /* BTLBF_ORDER_SERIAL applies k-mers one after another in buffer order on a single lane: the only
- * way incrementMin is reproducible (it is order-dependent). */
+ * way incrementMin is reproducible (it is order-dependent).
+ *
+ * BTLBF_ORDER_PARALLEL runs one k-mer per lane.  What a call then guarantees is what EVERY interleaving of the
+ * reference's per-probe atomics (CountingBloomFilter.hpp:135-183: byte loads and byte compare-and-swaps) can
+ * produce, and nothing more (tests/update_order_model.py states it as checkers):
+ *   incrementAll: exact.  Saturating +1 commutes, so the counters are those of the serial order.
+ *   incrementMin, counters before -> after one call, K = clean k-mers of the call, each with its h counters:
+ *     - no counter decreases, a counter at 255 stays at 255, a counter that no k-mer of the call probes is unchanged
+ *       (the four counters of a 32-bit word are updated with a word compare-and-swap that never carries);
+ *     - after <= what incrementAll of the same call would give, counter by counter;
+ *     - for every k-mer present: min(after[its counters]) >= min(min(before[its counters]) + 1, 255).  One call
+ *       raises the minimum of a k-mer that occurs in it by AT LEAST ONE, not by its multiplicity.  An insert is done
+ *       once ONE of its compare-and-swaps m -> m + 1 has made the change (one that changed nothing reads the minimum
+ *       again and retries).  With h >= 2, two concurrent inserts of one k-mer may both read the minimum m and each
+ *       win the compare-and-swap on a DIFFERENT counter of the k-mer, losing it on the other's: both are done, and
+ *       every counter stands at m + 1 after two occurrences -- in the reference as well.  With h = 1 there is one
+ *       counter to win, so the minimum rises by the full multiplicity (up to 255).  Callers that need
+ *       "n occurrences -> minimum >= n" with h >= 2 use incrementAll or the serial order;
+ *     - while no touched counter reaches 255: |K| <= sum(after) - sum(before) <= h * |K|.
+ *   insertAndCheck on a counting filter: out = 1 where the minimum before the call is >= threshold, out = 0 where
+ *     the minimum in incrementAll's result is < threshold, either answer in between; the counters as incrementMin. */
 enum { BTLBF_ORDER_PARALLEL = 0, BTLBF_ORDER_SERIAL = 1 };
 
 /* hipStreamPerThread (hip_runtime_api.h), for callers that do not include the HIP headers */
@@ -203,7 +223,17 @@ int btlbf_set_spaced_seeds(btlbf_filter* f, const char* const* seeds, unsigned n
  * contains: ntHashIterator + BloomFilter::contains (BloomFilter.hpp:252-262) /
  *           CountingBloomFilter::contains (CountingBloomFilter.hpp:190-196).
  * insert_and_check: BloomFilter::insertAndCheck (BloomFilter.hpp:200-214) -- bit of window p =
- *           all h bits were already set before this window's own writes.
+ *           all h bits were already set before this window's own writes.  The windows of a call run in
+ *           parallel order (one fetch-or per probe; there is no order argument), so with k-mers that share
+ *           bits the answers are those of SOME interleaving of the reference's fetch-ors:
+ *             - the filter afterwards is exactly what insert of the same windows gives;
+ *             - a clean window whose h bits were all set before the call reports 1;
+ *             - for every bit the call newly sets, at least one window that probes it reports 0 (the one whose
+ *               fetch-or came first); a window with a bit that was clear and that no other window probes reports 0;
+ *             - at most as many windows report 0 as bits were newly set (with h = 1: exactly as many), so a
+ *               k-mer repeated in the buffer is "new" once per newly set bit at the most, never once per copy;
+ *             - valid_bits = the clean windows, hit bits are 0 outside them, counts = {clean, set hit bits}.
+ *           A buffer without shared bit positions gives the serial order's answers bit for bit.
  * hit_bits / valid_bits may be NULL.  counts (may be NULL) receives {clean windows, hits}; it
  * lives in `mem` space and is overwritten. */
 int btlbf_insert_seqs(btlbf_filter* f, const char* seq, uint64_t len, const btlbf_layout* layout,
