@@ -104,6 +104,8 @@ _PROTOS = {
     "btlbf_mibf_query_seqs": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(Layout), C.c_uint, _P, _P, _P, _P, C.c_int, _P]),
     "btlbf_mibf_classify_seqs": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(Layout), C.POINTER(MibfClassifyParams), _P, _P,
                                            C.c_uint64, _P, _P, _P, _P, C.c_int, _P]),
+    "btlbf_mibf_classify_pairs": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(Layout), C.POINTER(MibfClassifyParams), _P, _P,
+                                            C.c_uint64, _P, _P, _P, _P, C.c_int, _P]),
     "btlbf_mibf_classify_paths": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "btlbf_mibf_stats": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "btlbf_mibf_id_counts": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),

@@ -34,7 +34,7 @@ struct btlbf_mibf {
 	// classify: the largest m_counts index over the data array, valid until the array next changes
 	bool max_id_known = false;
 	uint64_t max_id = 0;
-	uint64_t cls_paths[2] = {0, 0}; // the last classify call: sequences walked over an LDS / a global table
+	uint64_t cls_paths[2] = {0, 0}; // the last classify call: sequences (or pairs) walked over an LDS / a global table
 };
 
 namespace {
@@ -189,10 +189,10 @@ int mibf_batch_layout(const MibfSeqs& q, const MibfBatch& b, DevBuf& starts_buf,
 }
 
 // a plan that failed: no batch has run, so the ID array, the counts and the caller's outputs are as they were
-int mibf_too_big(const MibfPlan& plan)
+int mibf_too_big(const MibfPlan& plan, const char* unit = "sequence")
 {
-	return fail(BTLBF_ENOMEM, "miBF: sequence %llu does not fit the scratch budget (btlbf_mibf_set_scratch); nothing was "
-	            "changed", (unsigned long long)plan.too_big);
+	return fail(BTLBF_ENOMEM, "miBF: %s %llu does not fit the scratch budget (btlbf_mibf_set_scratch); nothing was "
+	            "changed", unit, (unsigned long long)plan.too_big);
 }
 
 MibfArgs mibf_args(const btlbf_mibf* m, const uint8_t* seq, uint64_t len, const LayoutParams& lay)
@@ -463,19 +463,26 @@ extern "C" int btlbf_mibf_query_seqs(btlbf_mibf* m, const char* seq, uint64_t le
 	return BTLBF_OK;
 }
 
-// MIBFQuerySupport<T>::query (MIBFQuerySupport.hpp:95-109) of every sequence: phase 1 is the MIBF_QUERY launch of
-// btlbf_mibf_query_seqs into scratch, phase 2 the walk of mibf_classify_kernels.hip, batch by batch under the budget
-extern "C" int btlbf_mibf_classify_seqs(btlbf_mibf* m, const char* seq, uint64_t len, const btlbf_layout* layout,
-                                        const btlbf_mibf_classify_params* p, const double* per_frame_prob,
-                                        const uint32_t* min_count_per_id, uint64_t n_ids, btlbf_mibf_hit* hits,
-                                        uint32_t* n_hits, uint32_t* sat_count, uint32_t* eval_count, int mem, void* stream)
+// MIBFQuerySupport<T>::query of every sequence (MIBFQuerySupport.hpp:95-109) or, with `pairs`, of every pair of
+// sequences 2i, 2i + 1 (:111-130): phase 1 is the MIBF_QUERY launch of btlbf_mibf_query_seqs into scratch, over the
+// sequence layout either way; phase 2 the walk of mibf_classify_kernels.hip / mibf_classify_pair_kernels.hip, batch by
+// batch under the budget.  A unit (a result row, an entry of the plan) is a sequence or a pair.
+static int mibf_classify(btlbf_mibf* m, const char* seq, uint64_t len, const btlbf_layout* layout,
+                         const btlbf_mibf_classify_params* p, const double* per_frame_prob,
+                         const uint32_t* min_count_per_id, uint64_t n_ids, btlbf_mibf_hit* hits, uint32_t* n_hits,
+                         uint32_t* sat_count, uint32_t* eval_count, int mem, void* stream, bool pairs)
 {
 	if (!m || (!seq && len) || !layout || !p || !per_frame_prob || !min_count_per_id || !hits || !n_hits || !sat_count ||
 	    !eval_count)
 		return fail(BTLBF_EINVAL, "null argument");
 	if (p->max_results == 0)
 		return fail(BTLBF_EINVAL, "miBF classify: max_results must be at least 1");
-	if (n_ids == 0 || n_ids > (1ull << (m->id_bytes * 8 - 1)))
+	if (n_ids == 0)
+		return fail(BTLBF_EINVAL, "miBF classify: n_ids must be at least 1");
+	if (pairs && ((layout->starts ? layout->n_seqs : layout->read_len ? len / layout->read_len : 0) & 1))
+		return fail(BTLBF_EINVAL, "miBF classify: pairs need an even number of sequences (mate 1, mate 2, ...); nothing "
+		            "was written");
+	if (n_ids > (1ull << (m->id_bytes * 8 - 1)))
 		return fail(BTLBF_EINVAL, "miBF classify: n_ids must be 1..2^%u for %u-byte ids, not %llu", m->id_bytes * 8 - 1,
 		            m->id_bytes, (unsigned long long)n_ids);
 	std::lock_guard<std::mutex> lk(m->mu);
@@ -486,7 +493,8 @@ extern "C" int btlbf_mibf_classify_seqs(btlbf_mibf* m, const char* seq, uint64_t
 	if (rc)
 		return rc;
 	m->cls_paths[0] = m->cls_paths[1] = 0;
-	if (c.q.n_seqs == 0)
+	const uint64_t n_units = pairs ? c.q.n_seqs / 2 : c.q.n_seqs;
+	if (n_units == 0)
 		return BTLBF_OK;
 	// every index the walk will use lies inside the caller's tables
 	if (!m->max_id_known) {
@@ -501,9 +509,10 @@ extern "C" int btlbf_mibf_classify_seqs(btlbf_mibf* m, const char* seq, uint64_t
 	if (m->max_id >= n_ids)
 		return fail(BTLBF_EINVAL, "miBF classify: the ID array holds id %llu, the tables %llu entries; nothing was written",
 		            (unsigned long long)m->max_id, (unsigned long long)n_ids);
-	const MibfPlan plan = mibf_plan_classify(c.q, mibf_budget(m->budget), m->k, m->h, m->id_bytes, n_ids);
+	const MibfPlan plan = pairs ? mibf_plan_classify_pairs(c.q, mibf_budget(m->budget), m->k, m->h, m->id_bytes, n_ids)
+	                            : mibf_plan_classify(c.q, mibf_budget(m->budget), m->k, m->h, m->id_bytes, n_ids);
 	if (!plan.ok())
-		return mibf_too_big(plan);
+		return mibf_too_big(plan, pairs ? "pair" : "sequence");
 	DevBuf vals, hit, valid, masks, big_list, big_off, big_tab, tables;
 	if (vals.alloc(plan.max_bytes * m->h * m->id_bytes) || hit.alloc(bitmap_bytes(plan.max_bytes)) ||
 	    valid.alloc(bitmap_bytes(plan.max_bytes)) || masks.alloc(plan.max_bytes) || big_list.alloc(plan.max_big * 4) ||
@@ -521,18 +530,20 @@ extern "C" int btlbf_mibf_classify_seqs(btlbf_mibf* m, const char* seq, uint64_t
 		d_minc = reinterpret_cast<const uint32_t*>(tables.as<uint8_t>() + n_ids * 8);
 	}
 	OutBuf o_hits, o_n, o_sat, o_eval;
-	if ((rc = o_hits.prepare(hits, c.q.n_seqs * p->max_results * sizeof(btlbf_mibf_hit), mem, true, s)) ||
-	    (rc = o_n.prepare(n_hits, c.q.n_seqs * 4, mem, true, s)) || (rc = o_sat.prepare(sat_count, c.q.n_seqs * 4, mem, true, s)) ||
-	    (rc = o_eval.prepare(eval_count, c.q.n_seqs * 4, mem, true, s)))
+	if ((rc = o_hits.prepare(hits, n_units * p->max_results * sizeof(btlbf_mibf_hit), mem, true, s)) ||
+	    (rc = o_n.prepare(n_hits, n_units * 4, mem, true, s)) || (rc = o_sat.prepare(sat_count, n_units * 4, mem, true, s)) ||
+	    (rc = o_eval.prepare(eval_count, n_units * 4, mem, true, s)))
 		return rc;
 	HIP_TRY(hipMemsetAsync(m->d_stat, 0, kMibfCallStat, s));
 	HIP_TRY(hipMemsetAsync(m->d_stat->cls_paths, 0, sizeof(MibfStat::cls_paths), s));
 	uint64_t big0 = 0; // the batch's first entry of the plan's big lists
 	for (const MibfBatch& b : plan.batches) {
-		const uint64_t b0 = c.q.start(b.s0), blen = c.q.start(b.s1) - b0;
+		// the batch in sequences: a plan of pairs counts pairs
+		const MibfBatch sq{pairs ? 2 * b.s0 : b.s0, pairs ? 2 * b.s1 : b.s1, b.big, b.slots};
+		const uint64_t b0 = c.q.start(sq.s0), blen = c.q.start(sq.s1) - b0;
 		DevBuf sb;
 		LayoutParams lay;
-		if ((rc = mibf_batch_layout(c.q, b, sb, lay, s)))
+		if ((rc = mibf_batch_layout(c.q, sq, sb, lay, s)))
 			return rc;
 		if (blen)
 			HIP_TRY(launch_mibf_seq(MIBF_QUERY, m->id_bytes,
@@ -570,7 +581,7 @@ extern "C" int btlbf_mibf_classify_seqs(btlbf_mibf* m, const char* seq, uint64_t
 			q.big_tab = big_tab.as<uint32_t>();
 			q.n_big = b.big;
 		}
-		HIP_TRY(launch_mibf_classify(m->id_bytes, q, s));
+		HIP_TRY(pairs ? launch_mibf_classify_pairs(m->id_bytes, q, s) : launch_mibf_classify(m->id_bytes, q, s));
 	}
 	unsigned long long paths[2] = {0, 0};
 	HIP_TRY(hipMemcpyAsync(paths, m->d_stat->cls_paths, sizeof paths, hipMemcpyDeviceToHost, s));
@@ -579,6 +590,24 @@ extern "C" int btlbf_mibf_classify_seqs(btlbf_mibf* m, const char* seq, uint64_t
 	HIP_TRY(hipStreamSynchronize(s)); // scratch is freed on return
 	memcpy(m->cls_paths, paths, sizeof paths);
 	return BTLBF_OK;
+}
+
+extern "C" int btlbf_mibf_classify_seqs(btlbf_mibf* m, const char* seq, uint64_t len, const btlbf_layout* layout,
+                                        const btlbf_mibf_classify_params* p, const double* per_frame_prob,
+                                        const uint32_t* min_count_per_id, uint64_t n_ids, btlbf_mibf_hit* hits,
+                                        uint32_t* n_hits, uint32_t* sat_count, uint32_t* eval_count, int mem, void* stream)
+{
+	return mibf_classify(m, seq, len, layout, p, per_frame_prob, min_count_per_id, n_ids, hits, n_hits, sat_count,
+	                     eval_count, mem, stream, false);
+}
+
+extern "C" int btlbf_mibf_classify_pairs(btlbf_mibf* m, const char* seq, uint64_t len, const btlbf_layout* layout,
+                                         const btlbf_mibf_classify_params* p, const double* per_frame_prob,
+                                         const uint32_t* min_count_per_id, uint64_t n_ids, btlbf_mibf_hit* hits,
+                                         uint32_t* n_hits, uint32_t* sat_count, uint32_t* eval_count, int mem, void* stream)
+{
+	return mibf_classify(m, seq, len, layout, p, per_frame_prob, min_count_per_id, n_ids, hits, n_hits, sat_count,
+	                     eval_count, mem, stream, true);
 }
 
 extern "C" int btlbf_mibf_classify_paths(btlbf_mibf* m, uint64_t* out2)

@@ -380,6 +380,9 @@ struct MibfClassifyArgs {
 	unsigned long long* stat;         // optional: {sequences walked over an LDS table, over a global table} +=
 };
 hipError_t launch_mibf_classify(int id_bytes, const MibfClassifyArgs& a, hipStream_t s);
+// the paired walk (mibf_classify_pair_kernels.hip): sequences 2i and 2i + 1 of the batch's layout are the mates of pair i;
+// row0, big_list and the stat words count pairs
+hipError_t launch_mibf_classify_pairs(int id_bytes, const MibfClassifyArgs& a, hipStream_t s);
 hipError_t launch_mibf_classify_maxid(int id_bytes, const void* data, uint64_t n, unsigned long long* out, hipStream_t s);
 
 } // namespace btlbf

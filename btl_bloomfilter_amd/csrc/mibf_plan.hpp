@@ -1,7 +1,8 @@
 // csrc/mibf_plan.hpp -- how the sequences of one miBF call are cut into batches under the scratch budget.  Plain integers
 // and host arithmetic only (no HIP header): tests/cpp/test_mibf_plan.cpp includes it alone.  One rule serves insert, serial
 // saturation and classify: cut [0, n_seqs) greedily into contiguous runs whose cost fits the budget, at least one sequence
-// each; a sequence that does not fit alone fails the plan, before any batch has run.
+// each; a sequence that does not fit alone fails the plan, before any batch has run.  Classifying read pairs plans the
+// same way with the pair as its unit (mibf_plan_classify_pairs; tests/cpp/test_mibf_plan_pairs.cpp).
 #pragma once
 #include <stdint.h>
 
@@ -112,6 +113,30 @@ inline MibfPlan mibf_plan_classify(const MibfSeqs& q, uint64_t budget, uint32_t 
 		const uint32_t cap = mibf_classify_cap(n, k, h, n_ids);
 		const uint64_t slots = cap > kMibfClsLdsSlots ? cap : 0;
 		return MibfCost{n * ((uint64_t)h * id_bytes + 2) + 64 + slots * kMibfClsSlotWords * 4 + (slots ? 12 : 0), slots};
+	});
+}
+
+// classify pairs: sequences 2i and 2i + 1 of q (n_seqs even) are the mates of pair i.  The unit is the pair, so no batch
+// separates two mates: the plan's s0, s1, big_seq and too_big count PAIRS, and a batch is sequences [2 * s0, 2 * s1).
+// The mates are adjacent in the buffer, so a pair is one range of n = n1 + n2 bytes; its table has
+// mibf_classify_cap(n, ...) slots (frames1 + frames2 <= n - k + 1).  Per pair: the bytes of phase 1 as for single reads,
+// 128 bytes for the two sequences' share of the layout and the result rows, and its table when that does not fit LDS.
+inline MibfPlan mibf_plan_classify_pairs(const MibfSeqs& q, uint64_t budget, uint32_t k, uint32_t h, uint32_t id_bytes,
+                                         uint64_t n_ids)
+{
+	MibfSeqs pairs;
+	pairs.n_seqs = q.n_seqs / 2;
+	if (q.read_len && q.read_len <= 0x7fffffffu) {
+		pairs.read_len = 2 * q.read_len;
+	} else {
+		pairs.starts.resize(pairs.n_seqs + 1);
+		for (uint64_t i = 0; i <= pairs.n_seqs; ++i)
+			pairs.starts[i] = q.read_len ? 2 * i * q.read_len : q.starts[2 * i];
+	}
+	return mibf_plan(pairs, budget, 0x3fffffffull, [=](uint64_t n) {
+		const uint32_t cap = mibf_classify_cap(n, k, h, n_ids);
+		const uint64_t slots = cap > kMibfClsLdsSlots ? cap : 0;
+		return MibfCost{n * ((uint64_t)h * id_bytes + 2) + 128 + slots * kMibfClsSlotWords * 4 + (slots ? 12 : 0), slots};
 	});
 }
 

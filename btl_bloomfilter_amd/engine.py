@@ -653,6 +653,20 @@ def hits_from_words(words):
     return w.view(HIT_DTYPE).reshape(w.shape[:-1])
 
 
+def interleave_mates(reads1, reads2):
+    """two lists of equal length (mate 1 and mate 2 of every pair; bytes, str or uint8 arrays) -> (buffer, starts): the
+    host buffer mate 1, mate 2, mate 1, ... and its 2 * n_pairs + 1 offsets, as MIBloomFilter.classifyPairs takes them"""
+    if len(reads1) != len(reads2):
+        raise ValueError("interleave_mates: %d first mates, %d second mates" % (len(reads1), len(reads2)))
+    as_u8 = lambda s: np.frombuffer(s.encode() if isinstance(s, str) else s, np.uint8) if isinstance(s, (str, bytes, bytearray)) \
+        else np.ascontiguousarray(s, np.uint8)
+    mates = [as_u8(s) for pair in zip(reads1, reads2) for s in pair]
+    starts = np.zeros(len(mates) + 1, np.uint64)
+    if mates:
+        starts[1:] = np.cumsum([m.size for m in mates])
+    return (np.concatenate(mates) if mates else np.zeros(0, np.uint8)), starts
+
+
 class MIBloomFilter(_Owned):
     """Multi-index Bloom filter over a stage-1 bit filter (btlbf_mibf_*; MIBloomFilter.hpp, MIBFConstructSupport.hpp,
     MIBFQuerySupport.hpp): an ID array of uint16 (id_bytes=2) or uint32 (id_bytes=4) in HBM, addressed by
@@ -746,11 +760,26 @@ class MIBloomFilter(_Owned):
         arguments.  n_hits counts every significant result; the first max_results of them are in hits.  Device
         input: the tables and results are torch tensors on that device (hits as int32[n_seqs, max_results, 4]:
         hits_from_words decodes a host copy)."""
+        return self._classify(self._L.btlbf_mibf_classify_seqs, 1, seqs, per_frame_prob, min_count, extra_count,
+                              extra_frame_limit, max_miss, min_frames, best_hit_agree, max_results, starts, read_len, stream)
+
+    def classifyPairs(self, seqs, per_frame_prob, min_count, *, extra_count=1.0, extra_frame_limit=0, max_miss=0,
+                      min_frames=1, best_hit_agree=False, max_results=8, starts=None, read_len=0, stream=None):
+        """MIBFQuerySupport<T>::query(itr1, itr2, minCount) (MIBFQuerySupport.hpp:111-130) of every read pair of an
+        interleaved buffer: sequences 2i and 2i + 1 are mate 1 and mate 2 of pair i (interleave_mates builds such a
+        buffer from two lists), their number must be even.  One walk per pair over the frames of both mates in turn,
+        into one set of counters and with one early stop.  Arguments and results as for classify, one row per pair."""
+        return self._classify(self._L.btlbf_mibf_classify_pairs, 2, seqs, per_frame_prob, min_count, extra_count,
+                              extra_frame_limit, max_miss, min_frames, best_hit_agree, max_results, starts, read_len, stream)
+
+    def _classify(self, fn, per_row, seqs, per_frame_prob, min_count, extra_count, extra_frame_limit, max_miss, min_frames,
+                  best_hit_agree, max_results, starts, read_len, stream):
+        """classify / classifyPairs: per_row sequences of the layout make one result row"""
         b = _Buf(seqs)
         lay, keep = _layout(starts, read_len, b.mem)
         if lay is None:
             raise ValueError("classify needs starts or read_len")
-        n_seqs = lay.n_seqs if starts is not None else b.nbytes // read_len
+        n_seqs = (lay.n_seqs if starts is not None else b.nbytes // read_len) // per_row
         n_ids = len(per_frame_prob)
         if len(min_count) != n_ids:
             raise ValueError("per_frame_prob and min_count must have one entry per id")
@@ -768,14 +797,14 @@ class MIBloomFilter(_Owned):
         n_hits, p_n = _out(b, n_seqs, np.uint32)
         sat, p_sat = _out(b, n_seqs, np.uint32)
         ev, p_ev = _out(b, n_seqs, np.uint32)
-        check(self._L.btlbf_mibf_classify_seqs(self._h, b.ptr, b.nbytes, C.byref(lay), C.byref(par), prob.ptr, minc.ptr,
-                                               n_ids, p_hits, p_n, p_sat, p_ev, b.mem, _stream_ptr(stream, b.keep)))
+        check(fn(self._h, b.ptr, b.nbytes, C.byref(lay), C.byref(par), prob.ptr, minc.ptr, n_ids, p_hits, p_n, p_sat, p_ev,
+                 b.mem, _stream_ptr(stream, b.keep)))
         if b.mem == DEVICE:
             return words, n_hits, sat, ev
         return hits_from_words(words), n_hits, sat, ev
 
     def classifyPaths(self):
-        """(sequences walked with their table in LDS, in HBM) of the last classify call"""
+        """(sequences, or pairs, walked with their table in LDS, in HBM) of the last classify / classifyPairs call"""
         out = (C.c_uint64 * 2)()
         check(self._L.btlbf_mibf_classify_paths(self._h, out))
         return int(out[0]), int(out[1])

@@ -429,12 +429,24 @@ int btlbf_mibf_load(btlbf_mibf** out, const char* path, btlbf_filter* f, unsigne
  *     reference built with contraction may fuse a - sqrt(a) * extra_count; the results agree bit for bit when
  *     extra_count is a power of two (0.5, 1, 2: the product is then exact), and only those values are pinned by tests.
  *   - candidates present but none passing isValid (the reference then reads signifResults[0] of an empty vector): 0 hits.
- *   - the paired overload query(itr1, itr2, minCount) (:111-130) is not provided.
  *   Errors: a null pointer, max_results == 0, n_ids == 0 or n_ids > 2^(bits(T)-1): EINVAL before any HIP call.  Sequences
  *   are classified in batches under the btlbf_mibf_set_scratch budget (per base h values, a hit mask and two bitmap bits;
  *   a sequence that can meet more than 255 distinct ids also a table of its own in HBM); a single sequence that does not
  *   fit returns ENOMEM with nothing written.
- * mibf_classify_paths : out2 = {sequences walked with their table in LDS, in HBM} of the last classify call. */
+ * mibf_classify_pairs : the paired overload query(itr1, itr2, minCount) (:111-130) of every read pair.  Sequences 2i and
+ *   2i + 1 of the layout (starts or read_len) are mate 1 and mate 2 of pair i, as in interleaved FASTQ; n_seqs must be
+ *   even (an odd count: EINVAL before any HIP call, nothing written).  The outputs have n_seqs / 2 rows.  A pair is ONE
+ *   walk over the frames of both mates, into one set of counters and with one early stop, in the reference's order
+ *   (:113-114): at an even frameCount the next frame of mate 1 if it has one, else of mate 2; at an odd frameCount the
+ *   next frame of mate 2 if it has one, else of mate 1; frameCount counts every frame taken.  A mate's frames are its
+ *   clean windows in position order, as above, and no window crosses the boundary between two mates.  Everything else --
+ *   updatesCounts, evalCount, max_miss, the stop, summarizeCandiates, the rules above, max_results, mem, stream, the
+ *   errors -- is the contract of mibf_classify_seqs applied to that frame sequence.  A pair without a frame in either
+ *   mate gives the empty result; (s, empty) and (empty, s) give what mibf_classify_seqs gives for s.  This is neither
+ *   the two mates classified alone nor the mates concatenated.  Batches are cut between pairs, never between the mates
+ *   of one; the table of a pair is sized for the bytes of both mates.
+ * mibf_classify_paths : out2 = {sequences walked with their table in LDS, in HBM} of the last classify call of either
+ *   kind (pairs, for mibf_classify_pairs). */
 typedef struct {
 	uint32_t id;
 	uint16_t count, nonSatCount, totalCount, totalNonSatCount, nonSatFrameCount, solidCount;
@@ -447,6 +459,10 @@ int btlbf_mibf_classify_seqs(btlbf_mibf* m, const char* seq, uint64_t len, const
                              const btlbf_mibf_classify_params* p, const double* per_frame_prob,
                              const uint32_t* min_count_per_id, uint64_t n_ids, btlbf_mibf_hit* hits, uint32_t* n_hits,
                              uint32_t* sat_count, uint32_t* eval_count, int mem, void* stream);
+int btlbf_mibf_classify_pairs(btlbf_mibf* m, const char* seq, uint64_t len, const btlbf_layout* layout,
+                              const btlbf_mibf_classify_params* p, const double* per_frame_prob,
+                              const uint32_t* min_count_per_id, uint64_t n_ids, btlbf_mibf_hit* hits, uint32_t* n_hits,
+                              uint32_t* sat_count, uint32_t* eval_count, int mem, void* stream);
 int btlbf_mibf_classify_paths(btlbf_mibf* m, uint64_t* out2);
 
 /* ---- multi-GPU hash-range sharding ------------------------------------------------

@@ -4,9 +4,12 @@
 //   * query(const std::vector<std::string>& seqs, minCount) classifies a whole batch in one call -- the one to use;
 //   * query(const std::string& seq, minCount) is the reference's per-read call and costs ONE GPU ROUND TRIP per read,
 //     like the iterator loops of INTEGRATION.md section 1: for porting and small inputs only.
-// getSatCount() / getEvalCount() answer for the last query(seq); the batched query returns them per read.
-// The rules for what the reference leaves open are in include/btlbf.h (btlbf_mibf_classify_seqs).  The paired overload
-// query(itr1, itr2, minCount) is not provided.  Errors follow detail.hpp.
+// The paired overload query(itr1, itr2, minCount) (one walk over both mates' frames in turn) is here
+//   * queryPairs(seqs1, seqs2, minCount) for a whole batch of pairs in one call (btlbf_mibf_classify_pairs), and
+//   * query(seq1, seq2, minCount), the per-pair call, again one GPU round trip each.
+// getSatCount() / getEvalCount() answer for the last query(seq) or query(seq1, seq2); the batched queries return them
+// per read or pair.  The rules for what the reference leaves open are in include/btlbf.h (btlbf_mibf_classify_seqs).
+// Errors follow detail.hpp.
 #ifndef BTLBF_MIBFQUERYSUPPORT_HPP
 #define BTLBF_MIBFQUERYSUPPORT_HPP
 #include "MIBloomFilter.hpp"
@@ -66,11 +69,60 @@ class MIBFQuerySupport
 			buf += seqs[i];
 			starts.push_back(buf.size());
 		}
+		return classify(buf, starts, seqs.size(), false, minCount);
+	}
+
+	// one call for all pairs: seqs1[i] and seqs2[i] are mate 1 and mate 2 of pair i; one result per pair
+	BatchResult queryPairs(const std::vector<std::string>& seqs1, const std::vector<std::string>& seqs2,
+	                       const std::vector<unsigned>& minCount) const
+	{
+		if (seqs1.size() != seqs2.size())
+			btlbf_shim::check(BTLBF_EINVAL);
+		std::string buf;
+		std::vector<uint64_t> starts(1, 0);
+		for (size_t i = 0; i < seqs1.size(); ++i) {
+			buf += seqs1[i];
+			starts.push_back(buf.size());
+			buf += seqs2[i];
+			starts.push_back(buf.size());
+		}
+		return classify(buf, starts, seqs1.size(), true, minCount);
+	}
+
+	// the reference's per-read call: one GPU round trip
+	const std::vector<QueryResult>& query(const std::string& seq, const std::vector<unsigned>& minCount)
+	{
+		BatchResult b = query(std::vector<std::string>(1, seq), minCount);
+		m_signifResults = b.results[0];
+		m_satCount = b.satCount[0];
+		m_evalCount = b.evalCount[0];
+		return m_signifResults;
+	}
+
+	// the reference's per-pair call (:111-130): one GPU round trip
+	const std::vector<QueryResult>&
+	query(const std::string& seq1, const std::string& seq2, const std::vector<unsigned>& minCount)
+	{
+		BatchResult b = queryPairs(std::vector<std::string>(1, seq1), std::vector<std::string>(1, seq2), minCount);
+		m_signifResults = b.results[0];
+		m_satCount = b.satCount[0];
+		m_evalCount = b.evalCount[0];
+		return m_signifResults;
+	}
+
+	unsigned getSatCount() const { return m_satCount; }
+	unsigned getEvalCount() const { return m_evalCount; }
+
+  private:
+	// the sequences of buf (starts: their offsets) as n rows of single reads or of pairs
+	BatchResult classify(const std::string& buf, const std::vector<uint64_t>& starts, size_t n, bool pairs,
+	                     const std::vector<unsigned>& minCount) const
+	{
 		btlbf_layout l;
 		l.starts = &starts[0];
-		l.n_seqs = seqs.size();
+		l.n_seqs = starts.size() - 1;
 		l.read_len = 0;
-		const size_t n = seqs.size(), mr = m_par.max_results;
+		const size_t mr = m_par.max_results;
 		std::vector<btlbf_mibf_hit> hits(n * mr + 1);
 		BatchResult out;
 		out.nResults.assign(n + 1, 0);
@@ -79,9 +131,9 @@ class MIBFQuerySupport
 		std::vector<uint32_t> mc(minCount.begin(), minCount.end());
 		if (mc.size() != m_perFrameProb.size())
 			btlbf_shim::check(BTLBF_EINVAL);
-		btlbf_shim::check(btlbf_mibf_classify_seqs(m_miBF.handle(), buf.empty() ? "" : buf.data(), buf.size(), &l, &m_par,
-		                                           m_perFrameProb.data(), mc.data(), mc.size(), &hits[0], &out.nResults[0],
-		                                           &out.satCount[0], &out.evalCount[0], BTLBF_HOST, nullptr));
+		btlbf_shim::check((pairs ? btlbf_mibf_classify_pairs : btlbf_mibf_classify_seqs)(
+		    m_miBF.handle(), buf.empty() ? "" : buf.data(), buf.size(), &l, &m_par, m_perFrameProb.data(), mc.data(), mc.size(),
+		    &hits[0], &out.nResults[0], &out.satCount[0], &out.evalCount[0], BTLBF_HOST, nullptr));
 		out.nResults.resize(n);
 		out.satCount.resize(n);
 		out.evalCount.resize(n);
@@ -98,20 +150,6 @@ class MIBFQuerySupport
 		return out;
 	}
 
-	// the reference's per-read call: one GPU round trip
-	const std::vector<QueryResult>& query(const std::string& seq, const std::vector<unsigned>& minCount)
-	{
-		BatchResult b = query(std::vector<std::string>(1, seq), minCount);
-		m_signifResults = b.results[0];
-		m_satCount = b.satCount[0];
-		m_evalCount = b.evalCount[0];
-		return m_signifResults;
-	}
-
-	unsigned getSatCount() const { return m_satCount; }
-	unsigned getEvalCount() const { return m_evalCount; }
-
-  private:
 	const MIBloomFilter<T>& m_miBF;
 	const std::vector<double> m_perFrameProb;
 	btlbf_mibf_classify_params m_par;
