@@ -15,6 +15,7 @@ INCREMENT_MIN, INCREMENT_ALL = 0, 1
 ORDER_PARALLEL, ORDER_SERIAL = 0, 1
 OK, EINVAL, ENOMEM, EIO, EFORMAT, EHIP = range(6)
 INSERT_AUTO, INSERT_DIRECT, INSERT_PARTITIONED = 0, 1, 2
+FASTX_LINES, FASTX_PAGEABLE, FASTX_WHOLE, CLASSIFY_INTERLEAVED = 1, 2, 4, 1 << 8
 PROF_SLOTS = 10
 PROF_NAMES = ["insert_direct", "query_direct", "insert_hash", "insert_split", "insert_apply", "query_hash",
               "query_split", "query_test", "query_resolve", "other"]
@@ -108,6 +109,19 @@ _PROTOS = {
                                             C.c_uint64, _P, _P, _P, _P, C.c_int, _P]),
     "btlbf_mibf_classify_paths": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "btlbf_mibf_stats": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "btlbf_mibf_frame_probs": (C.c_int, [_P, C.c_uint, _P, C.c_uint64, C.POINTER(C.c_double)]),
+    "btlbf_mibf_prob_single_frame": (C.c_double, [C.c_double, C.c_uint, C.c_double, C.c_uint]),
+    "btlbf_interleave_mates": (C.c_int, [_P, _P, _P, _P, C.c_uint64, _P, _P, C.c_int, C.c_int, _P]),
+    "btlbf_mibf_classify_tally": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint64, _P, _P, _P, C.c_int,
+                                            C.c_int, _P]),
+    "btlbf_mibf_classify_fastx_open": (C.c_int, [C.POINTER(_P), _P, C.c_char_p, C.c_char_p, C.c_uint32,
+                                                 C.POINTER(MibfClassifyParams), _P, _P, C.c_uint64, C.c_uint64]),
+    "btlbf_mibf_classify_fastx_next": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(_P),
+                                                 C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
+    "btlbf_mibf_classify_fastx_tally": (C.c_int, [_P, _P, _P, _P]),
+    "btlbf_mibf_classify_fastx_close": (None, [_P]),
+    "btlbf_mibf_classify_fastx": (C.c_int, [_P, C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(MibfClassifyParams), _P, _P,
+                                            C.c_uint64, C.c_uint64, _P, _P, _P, C.POINTER(FastxStats)]),
     "btlbf_mibf_id_counts": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "btlbf_mibf_download": (C.c_int, [_P, _P]),
     "btlbf_mibf_upload": (C.c_int, [_P, _P]),

@@ -72,8 +72,8 @@ struct btlbf_fastx {
 	bool seq_open = false;  // a sequence is being appended (FASTA records span lines)
 	uint64_t seq_in_batch = 0; // bases of the open sequence that sit in the current batch
 	bool cont = false;      // the previous batch was cut inside a sequence: this one continues it ...
-	char* carry = nullptr;  // ... starting with its last k-1 bases again
-	uint32_t carry_len = 0;
+	char* carry = nullptr;  // ... starting with its last k-1 bases again (BTLBF_FASTX_WHOLE: with all it had so far)
+	uint64_t carry_len = 0;
 	uint64_t n_records = 0;
 	double seconds_parse = 0;
 
@@ -202,7 +202,7 @@ int open_impl(btlbf_fastx** out, const char* path, uint32_t flags, uint32_t k, u
 		return btlbf_set_error(BTLBF_EINVAL, "fastx_open: null argument or k == 0");
 	if (batch_bytes == 0)
 		batch_bytes = 256ull << 20;
-	if (batch_bytes < 4ull * k + 64)
+	if (batch_bytes < 4ull * k + 64 && !(flags & BTLBF_FASTX_WHOLE)) // whole records have no overlap to make room for
 		return btlbf_set_error(BTLBF_EINVAL, "fastx_open: batch of %llu bytes is too small for k = %u",
 		                       (unsigned long long)batch_bytes, k);
 	btlbf_fastx* r = new (std::nothrow) btlbf_fastx;
@@ -233,7 +233,7 @@ int open_impl(btlbf_fastx** out, const char* path, uint32_t flags, uint32_t k, u
 	r->cap_bases = batch_bytes;
 	r->cap_seqs = batch_bytes / 16 + 1024;
 	r->in = static_cast<char*>(malloc(kInBuf));
-	r->carry = static_cast<char*>(malloc(k));
+	r->carry = static_cast<char*>(malloc((flags & BTLBF_FASTX_WHOLE) ? (size_t)batch_bytes + k : k));
 	bool ok = r->in && r->carry;
 	// pinned memory when a GPU is there (async copies); plain memory otherwise (parser-only use)
 	int ndev = 0;
@@ -292,6 +292,7 @@ extern "C" int btlbf_fastx_next(btlbf_fastx* r, const char** bases, uint64_t* n_
 	uint64_t* st = r->starts[r->cur];
 	uint64_t nb = 0, ns = 0;
 	const bool per_line = (r->flags & BTLBF_FASTX_LINES) != 0;
+	const bool whole = (r->flags & BTLBF_FASTX_WHOLE) != 0;
 	auto open_seq = [&]() {
 		st[ns++] = nb;
 		r->seq_open = true;
@@ -308,8 +309,20 @@ extern "C" int btlbf_fastx_next(btlbf_fastx* r, const char** bases, uint64_t* n_
 	auto cut = [&]() {
 		const uint64_t c = r->seq_in_batch < r->k - 1 ? r->seq_in_batch : r->k - 1;
 		memcpy(r->carry, out + nb - c, c);
-		r->carry_len = (uint32_t)c;
+		r->carry_len = c;
 		r->cont = true;
+	};
+	// BTLBF_FASTX_WHOLE: the open sequence does not fit the rest of this batch.  It leaves the batch and opens the next
+	// one with the bases it had so far; one that has the batch to itself fits no batch
+	auto defer = [&]() -> bool {
+		if (st[ns - 1] == 0)
+			return false;
+		nb -= r->seq_in_batch;
+		memcpy(r->carry, out + nb, r->seq_in_batch);
+		r->carry_len = r->seq_in_batch;
+		r->cont = true;
+		--ns;
+		return true;
 	};
 	while (!full) {
 		if (r->in_pos == r->in_len && !refill(r))
@@ -320,7 +333,15 @@ extern "C" int btlbf_fastx_next(btlbf_fastx* r, const char** bases, uint64_t* n_
 			const char c = *p;
 			if (c == '\n' || c == '\r') {
 				// empty line: ignored, except that an empty FASTQ line still is one of the record's four
-				// (zero-length reads exist)
+				// (zero-length reads exist).  BTLBF_FASTX_WHOLE delivers such a read as an empty sequence: its record is a
+				// row of the classifier, and its mate's partner
+				if (c == '\n' && whole && r->fmt == btlbf_fastx::FASTQ && r->fq_line == 1) {
+					if (ns >= r->cap_seqs) {
+						full = true;
+						break;
+					}
+					open_seq();
+				}
 				++r->in_pos;
 				if (c == '\n' && r->fmt == btlbf_fastx::FASTQ)
 					r->fq_line = (r->fq_line + 1) & 3;
@@ -390,6 +411,13 @@ extern "C" int btlbf_fastx_next(btlbf_fastx* r, const char** bases, uint64_t* n_
 				}
 			}
 			const uint64_t room = r->cap_bases - nb;
+			if (take > room && whole) {
+				if (!defer())
+					return btlbf_set_error(BTLBF_EINVAL, "fastx_next: record %llu is longer than a batch of %llu bytes and "
+					                       "BTLBF_FASTX_WHOLE does not cut sequences",
+					                       (unsigned long long)r->n_records, (unsigned long long)r->cap_bases);
+				break;
+			}
 			if (take > room) {
 				take = room;
 				n = take;
@@ -410,7 +438,7 @@ extern "C" int btlbf_fastx_next(btlbf_fastx* r, const char** bases, uint64_t* n_
 			r->st = btlbf_fastx::LINE_START;
 			if (r->fmt == btlbf_fastx::FASTQ)
 				r->fq_line = (r->fq_line + 1) & 3;
-			if (nb == r->cap_bases)
+			if (nb == r->cap_bases && !(whole && r->seq_open && r->fmt == btlbf_fastx::FASTA && !per_line))
 				full = true; // exactly full at a line end: nothing to carry unless the record goes on
 			if (full && r->seq_open && r->fmt == btlbf_fastx::FASTA && !per_line)
 				cut(); // the record may go on in the next line

@@ -418,4 +418,11 @@ int split_contains(btlbf_filter* f, const SeqArgs& a, int direct_op, hipStream_t
 // owns, and *ones the popcount.  After an allocation that failed *d_il is null; after a build that failed it is not.
 hipError_t rank_build(const btlbf_filter* f, uint64_t** d_il, uint64_t* n_blocks, uint64_t* ones);
 
+// What the other miBF host units (host_mibf_probs.cpp, host_mibf_fastx.cpp) need of the object, which host_mibf.cpp keeps
+// to itself: its device, its id width, and the largest m_counts index over the data array -- the reduction classify caches
+// until the array next changes.
+int mibf_device(const btlbf_mibf* m);
+unsigned mibf_id_bytes(const btlbf_mibf* m);
+int mibf_max_id(btlbf_mibf* m, uint64_t* max_id);
+
 } // namespace btlbf

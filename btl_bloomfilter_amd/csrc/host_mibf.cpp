@@ -227,6 +227,21 @@ MibfArgs mibf_query_args(const btlbf_mibf* m, const uint8_t* seq, uint64_t len, 
 	return a;
 }
 
+// the largest m_counts index over the data array into m->max_id, cached until the array next changes; m->mu is held
+int mibf_max_id_locked(btlbf_mibf* m, hipStream_t s)
+{
+	if (m->max_id_known)
+		return BTLBF_OK;
+	HIP_TRY(hipMemsetAsync(&m->d_stat->max_id, 0, sizeof(MibfStat::max_id), s));
+	HIP_TRY(launch_mibf_classify_maxid(m->id_bytes, m->d_data, m->pop, &m->d_stat->max_id, s));
+	unsigned long long mx = 0;
+	HIP_TRY(hipMemcpyAsync(&mx, &m->d_stat->max_id, sizeof mx, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	m->max_id = mx;
+	m->max_id_known = true;
+	return BTLBF_OK;
+}
+
 unsigned bit_len(uint64_t x) { return x ? 64 - __builtin_clzll(x) : 0; }
 
 #pragma pack(push, 1)
@@ -243,6 +258,17 @@ static_assert(sizeof(MibfFileHeader) == 32, "packed miBF header");
 constexpr uint32_t kMibfVersion = 1;
 
 } // namespace
+
+int btlbf::mibf_device(const btlbf_mibf* m) { return m->device; }
+unsigned btlbf::mibf_id_bytes(const btlbf_mibf* m) { return m->id_bytes; }
+int btlbf::mibf_max_id(btlbf_mibf* m, uint64_t* max_id)
+{
+	std::lock_guard<std::mutex> lk(m->mu);
+	DeviceGuard g(m->device);
+	const int rc = mibf_max_id_locked(m, nullptr);
+	*max_id = m->max_id;
+	return rc;
+}
 
 extern "C" int btlbf_mibf_create(btlbf_mibf** out, btlbf_filter* f, unsigned id_bytes)
 {
@@ -497,15 +523,8 @@ static int mibf_classify(btlbf_mibf* m, const char* seq, uint64_t len, const btl
 	if (n_units == 0)
 		return BTLBF_OK;
 	// every index the walk will use lies inside the caller's tables
-	if (!m->max_id_known) {
-		HIP_TRY(hipMemsetAsync(&m->d_stat->max_id, 0, sizeof(MibfStat::max_id), s));
-		HIP_TRY(launch_mibf_classify_maxid(m->id_bytes, m->d_data, m->pop, &m->d_stat->max_id, s));
-		unsigned long long mx = 0;
-		HIP_TRY(hipMemcpyAsync(&mx, &m->d_stat->max_id, sizeof mx, hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		m->max_id = mx;
-		m->max_id_known = true;
-	}
+	if ((rc = mibf_max_id_locked(m, s)))
+		return rc;
 	if (m->max_id >= n_ids)
 		return fail(BTLBF_EINVAL, "miBF classify: the ID array holds id %llu, the tables %llu entries; nothing was written",
 		            (unsigned long long)m->max_id, (unsigned long long)n_ids);

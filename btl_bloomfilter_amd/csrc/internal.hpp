@@ -385,4 +385,13 @@ hipError_t launch_mibf_classify(int id_bytes, const MibfClassifyArgs& a, hipStre
 hipError_t launch_mibf_classify_pairs(int id_bytes, const MibfClassifyArgs& a, hipStream_t s);
 hipError_t launch_mibf_classify_maxid(int id_bytes, const void* data, uint64_t n, unsigned long long* out, hipStream_t s);
 
+// the file classifier's device helpers (mibf_stream_kernels.hip; contracts: btlbf_interleave_mates and
+// btlbf_mibf_classify_tally in include/btlbf.h).  hits: btlbf_mibf_hit[n_rows * max_results]
+hipError_t launch_interleave_mates(const uint8_t* seq1, const uint64_t* starts1, const uint8_t* seq2,
+                                   const uint64_t* starts2, uint64_t n_pairs, uint8_t* out, uint64_t* out_starts,
+                                   hipStream_t s);
+hipError_t launch_mibf_tally(const void* hits, const uint32_t* n_hits, const uint32_t* sat_count,
+                             const uint32_t* eval_count, uint64_t n_rows, uint32_t max_results, uint64_t n_ids,
+                             unsigned long long* best, unsigned long long* any, unsigned long long* totals, hipStream_t s);
+
 } // namespace btlbf

@@ -614,14 +614,15 @@ def count_per_seq(hit_bits, valid_bits, n_bytes, k, starts=None, read_len=0, dev
     return hits, valid
 
 
-def fastx_batches(path, k, per_line=False, batch_bytes=0, pageable=True, byte_range=None, fmt=None):
+def fastx_batches(path, k, per_line=False, batch_bytes=0, pageable=True, byte_range=None, fmt=None, whole=False):
     """Iterate over the parser's batches as (bases: bytes, starts: list[int]) -- the host-side reader
     behind insertFile (btlbf_fastx_open / btlbf_fastx_next); needs no GPU.  byte_range=(begin, end) with
     fmt in {"fasta", "fastq", "plain"}: only the records that start in that byte range of an
-    uncompressed file (btlbf_fastx_open_range, the unit of parallel parsing)."""
+    uncompressed file (btlbf_fastx_open_range, the unit of parallel parsing).  whole: BTLBF_FASTX_WHOLE, no sequence is
+    cut at a batch boundary (one longer than a batch is an error) and an empty FASTQ read is an empty sequence."""
     L = _lib.load()
     r = C.c_void_p()
-    flags = (1 if per_line else 0) | (2 if pageable else 0)
+    flags = (1 if per_line else 0) | (2 if pageable else 0) | (_lib.FASTX_WHOLE if whole else 0)
     if byte_range is None:
         check(L.btlbf_fastx_open(C.byref(r), str(path).encode(), flags, int(k), int(batch_bytes)))
     else:
@@ -665,6 +666,51 @@ def interleave_mates(reads1, reads2):
     if mates:
         starts[1:] = np.cumsum([m.size for m in mates])
     return (np.concatenate(mates) if mates else np.zeros(0, np.uint8)), starts
+
+
+def interleave_mates_device(seq1, starts1, seq2, starts2, stream=None):
+    """interleave_mates on the GPU (btlbf_interleave_mates): two ragged buffers -- torch uint8 tensors of bases and int64
+    tensors of n_pairs + 1 offsets on one device, any alignment -- -> (buffer, starts) as classifyPairs takes them"""
+    import torch
+
+    n_pairs = starts1.numel() - 1
+    if starts2.numel() - 1 != n_pairs:
+        raise ValueError("interleave_mates_device: %d first mates, %d second mates" % (n_pairs, starts2.numel() - 1))
+    bufs = [seq1, seq2, starts1.contiguous(), starts2.contiguous()]
+    if not all(_is_torch_cuda(x) for x in bufs) or not seq1.is_contiguous() or not seq2.is_contiguous():
+        raise ValueError("interleave_mates_device takes contiguous tensors on the GPU")
+    out = torch.empty(seq1.numel() + seq2.numel(), dtype=torch.uint8, device=seq1.device)
+    out_starts = torch.empty(2 * n_pairs + 1, dtype=torch.int64, device=seq1.device)
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    check(_lib.load().btlbf_interleave_mates(ptr(seq1), ptr(bufs[2]), ptr(seq2), ptr(bufs[3]), n_pairs, ptr(out),
+                                             ptr(out_starts), DEVICE, seq1.device.index or 0, _stream_ptr(stream, seq1)))
+    return out, out_starts
+
+
+def classify_tally(hits, n_hits, sat_count, eval_count, n_ids, best=None, any_=None, totals=None, device=0, stream=None):
+    """btlbf_mibf_classify_tally: adds the summary of one batch of classify results to (best[n_ids], any[n_ids],
+    totals[6]) and returns them.  Host results (hits as HIT_DTYPE or 32-bit words) with uint64 numpy totals, or device
+    results (classify's tensors) with int64 tensors; the totals are made, zeroed, where they are not given."""
+    b = _Buf(hits.view(np.uint32) if isinstance(hits, np.ndarray) else hits, np.uint32)
+    n_rows = len(n_hits)
+    max_results = (b.nbytes // 16) // n_rows if n_rows else max(int(np.prod(hits.shape[1:2])), 1)
+    outs = []
+    for x, n in ((best, n_ids), (any_, n_ids), (totals, 6)):
+        if x is None:
+            x, _ = _out(b, n, np.uint64)
+        outs.append(x)
+    args = [_Buf(x, np.uint32) for x in (n_hits, sat_count, eval_count)] + \
+        [_Buf(x, np.uint64) if b.mem == HOST else _Buf(x) for x in outs]
+    if any(a.mem != b.mem for a in args):
+        raise ValueError("classify_tally: all arrays live in one memory space")
+    for x, a in zip(outs, args[3:]):
+        if b.mem == HOST and a.keep is not x:
+            raise ValueError("classify_tally: the totals are contiguous uint64 arrays")
+    check(_lib.load().btlbf_mibf_classify_tally(b.ptr, args[0].ptr, args[1].ptr, args[2].ptr, n_rows, max(max_results, 1),
+                                                int(n_ids), args[3].ptr, args[4].ptr, args[5].ptr, b.mem,
+                                                (b.keep.device.index or 0) if b.mem == DEVICE else device,
+                                                _stream_ptr(stream, b.keep)))
+    return tuple(outs)
 
 
 class MIBloomFilter(_Owned):
@@ -803,6 +849,51 @@ class MIBloomFilter(_Owned):
             return words, n_hits, sat, ev
         return hits_from_words(words), n_hits, sat, ev
 
+    def calcFrameProbs(self, n_ids, allowed_miss=0):
+        """calcFrameProbs (MIBloomFilter.hpp:664-679) for a perFrameProb vector of n_ids entries -> (probs[n_ids],
+        sat_prop).  probs[0] is not written by the reference and is 0 here."""
+        probs = np.zeros(max(int(n_ids), 1), np.float64)
+        sat = C.c_double()
+        check(self._L.btlbf_mibf_frame_probs(self._h, int(allowed_miss), C.c_void_p(probs.ctypes.data), int(n_ids),
+                                             C.byref(sat)))
+        return probs[: int(n_ids)], sat.value
+
+    @staticmethod
+    def calcProbSingleFrame(occupancy, hash_num, freq, allowed_misses):
+        """calcProbSingleFrame (MIBloomFilter.hpp:65-77)"""
+        return _lib.load().btlbf_mibf_prob_single_frame(float(occupancy), int(hash_num), float(freq), int(allowed_misses))
+
+    def classifyFile(self, path, per_frame_prob, min_count, *, path2=None, interleaved=False, batch_bytes=0,
+                     summary_only=False, per_line=False, extra_count=1.0, extra_frame_limit=0, max_miss=0, min_frames=1,
+                     best_hit_agree=False, max_results=8):
+        """classify / classifyPairs of the reads of a FASTA / FASTQ file (plain or gzip), in file order
+        (btlbf_mibf_classify_fastx_*): single reads; with path2, record i of both files as pair i; with interleaved,
+        records 2i and 2i + 1 of the one file.  An iterator of (first_row, hits, n_hits, sat_count, eval_count) per batch
+        of at most batch_bytes bases (0: 64 MiB): numpy arrays as classify returns them, copied out of the library's
+        buffers; its tally() gives the running summary of the rows delivered so far, close() ends it early.  With
+        summary_only=True no per-read result leaves the GPU and the call returns (best[n_ids], any[n_ids], totals):
+        reads per id by their first result, by any of their first max_results results, and {rows, without a result,
+        with several, with more than max_results, sum of satCount, sum of
+        evalCount}.  The classify keywords are those of classify."""
+        n_ids = len(per_frame_prob)
+        if len(min_count) != n_ids:
+            raise ValueError("per_frame_prob and min_count must have one entry per id")
+        prob = np.ascontiguousarray(per_frame_prob, np.float64)
+        minc = np.ascontiguousarray(min_count, np.uint32)
+        par = _lib.MibfClassifyParams(float(extra_count), int(extra_frame_limit), int(max_miss), int(min_frames),
+                                      int(bool(best_hit_agree)), int(max_results))
+        flags = (_lib.FASTX_LINES if per_line else 0) | (_lib.CLASSIFY_INTERLEAVED if interleaved else 0)
+        p1 = str(path).encode()
+        p2 = str(path2).encode() if path2 is not None else None
+        if summary_only:
+            best, any_, totals = np.zeros(max(n_ids, 1), np.uint64), np.zeros(max(n_ids, 1), np.uint64), np.zeros(6, np.uint64)
+            check(self._L.btlbf_mibf_classify_fastx(self._h, p1, p2, flags, C.byref(par), C.c_void_p(prob.ctypes.data),
+                                                    C.c_void_p(minc.ctypes.data), n_ids, int(batch_bytes),
+                                                    C.c_void_p(best.ctypes.data), C.c_void_p(any_.ctypes.data),
+                                                    C.c_void_p(totals.ctypes.data), None))
+            return best[:n_ids], any_[:n_ids], totals
+        return _ClassifyFile(self, p1, p2, flags, par, prob, minc, n_ids, int(batch_bytes))
+
     def classifyPaths(self):
         """(sequences, or pairs, walked with their table in LDS, in HBM) of the last classify / classifyPairs call"""
         out = (C.c_uint64 * 2)()
@@ -849,3 +940,43 @@ class MIBloomFilter(_Owned):
 
     def store(self, path):
         check(self._L.btlbf_mibf_store(self._h, str(path).encode()))
+
+
+class _ClassifyFile(_Owned):
+    """the iterator behind MIBloomFilter.classifyFile: one batch per step, tally() for the running summary"""
+
+    _destroy = "btlbf_mibf_classify_fastx_close"
+
+    def __init__(self, mibf, p1, p2, flags, par, prob, minc, n_ids, batch_bytes):
+        self._L = _lib.load()
+        self._mibf = mibf  # the handle uses it until close()
+        self.n_ids, self.max_results = n_ids, par.max_results
+        h = C.c_void_p()
+        check(self._L.btlbf_mibf_classify_fastx_open(C.byref(h), mibf._h, p1, p2, flags, C.byref(par),
+                                                     C.c_void_p(prob.ctypes.data), C.c_void_p(minc.ctypes.data), n_ids,
+                                                     batch_bytes))
+        self._h = h
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if not self._h:
+            raise StopIteration
+        first, n = C.c_uint64(), C.c_uint64()
+        ptrs = [C.c_void_p() for _ in range(4)]
+        check(self._L.btlbf_mibf_classify_fastx_next(self._h, C.byref(first), C.byref(n), *[C.byref(p) for p in ptrs]))
+        n = n.value
+        if n == 0:
+            raise StopIteration
+        copy = lambda p, shape, dt: np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), shape=shape).astype(dt, copy=True)
+        words = copy(ptrs[0], (n, self.max_results, 4), np.uint32)
+        return (first.value, hits_from_words(words)) + tuple(copy(p, (n,), np.uint32) for p in ptrs[1:])
+
+    def tally(self):
+        """(best, any, totals) over the rows delivered so far (btlbf_mibf_classify_fastx_tally)"""
+        best, any_, totals = (np.zeros(max(self.n_ids, 1), np.uint64), np.zeros(max(self.n_ids, 1), np.uint64),
+                              np.zeros(6, np.uint64))
+        check(self._L.btlbf_mibf_classify_fastx_tally(self._h, C.c_void_p(best.ctypes.data), C.c_void_p(any_.ctypes.data),
+                                                      C.c_void_p(totals.ctypes.data)))
+        return best[: self.n_ids], any_[: self.n_ids], totals

@@ -465,6 +465,44 @@ int btlbf_mibf_classify_pairs(btlbf_mibf* m, const char* seq, uint64_t len, cons
                               uint32_t* sat_count, uint32_t* eval_count, int mem, void* stream);
 int btlbf_mibf_classify_paths(btlbf_mibf* m, uint64_t* out2);
 
+/* ---- frame probabilities and the device helpers of the file classifier ----------------------------------
+ * mibf_frame_probs : MIBloomFilter<T>::calcFrameProbs(frameProbs, allowedMiss) (MIBloomFilter.hpp:664-679) over
+ *   calcProbSingleFrame (:65-77), getIDCounts (:539-551) and nChoosek (:781-796); n = frameProbs.size().
+ *   occupancy = getPop() / size() (set bits of the bit vector over its length); countTable = getIDCounts over n bins, from
+ *   the device histogram of btlbf_mibf_id_counts; sum = countTable[1] + ... + countTable[n-1] (the reference's loop starts
+ *   at 1: entries of id 0 are not counted); *sat_prop = saturated entries / sum; frame_probs[i] =
+ *   calcProbSingleFrame(occupancy, h, countTable[i] / sum, allowed_miss) for 1 <= i < n.  frame_probs[0] is NOT written,
+ *   as in the reference.  Host arithmetic in double in the reference's order of operations, pow from libm, without
+ *   contraction (the compareStdErr rule above); nChoosek in int, as the reference computes it.
+ *   Where the reference has undefined behaviour this call returns EINVAL with nothing written:
+ *   - the largest id index of the data array (the cached reduction of mibf_classify_seqs) is >= n: getIDCounts would
+ *     index past countTable;
+ *   - allowed_miss > h: the reference's unsigned loop start h - allowed_miss wraps;
+ *   - sum == 0: both divisions are by zero;
+ *   - a null pointer or n == 0 (checked before any HIP call).
+ * mibf_prob_single_frame : calcProbSingleFrame itself, the same arithmetic, for one frequency (no device work).
+ *   allowed_misses > hash_num gives 0, as the reference's wrapped loop does.
+ * interleave_mates : the interleaved buffer mibf_classify_pairs takes, built on the device from two ragged buffers
+ *   (starts1 / starts2: n_pairs + 1 offsets each, starts*[0] == 0): out = mate 1 of pair 0, mate 2 of pair 0, mate 1 of
+ *   pair 1, ...; out_starts[2i] = starts1[i] + starts2[i], out_starts[2i+1] = starts1[i+1] + starts2[i],
+ *   out_starts[2 n_pairs] = starts1[n_pairs] + starts2[n_pairs] (2 n_pairs + 1 entries).  Any alignment of the four
+ *   buffers.  mem == BTLBF_HOST: the buffers are staged.  Null pointers: EINVAL before any HIP call (seq1, seq2 and out
+ *   may be null only when they hold no byte).
+ * mibf_classify_tally : adds the summary of one batch of classify results (n_rows rows of max_results records) to
+ *   running totals: best[id] += 1 for the id of the first record of every row with n_hits >= 1; any[id] += 1 for each of
+ *   the first min(n_hits, max_results) records of every row; totals6 += {rows, rows with n_hits == 0, rows with
+ *   n_hits > 1, rows with n_hits > max_results, sum of sat_count, sum of eval_count}.  best and any have n_ids entries;
+ *   an id >= n_ids (classify cannot produce one) is ignored.  All arrays in memory space mem; with BTLBF_HOST they are
+ *   staged and the call returns when the totals are back.  Null pointers (the four result arrays may be null when
+ *   n_rows == 0), max_results == 0 or n_ids == 0: EINVAL before any HIP call. */
+int btlbf_mibf_frame_probs(btlbf_mibf* m, unsigned allowed_miss, double* frame_probs, uint64_t n, double* sat_prop);
+double btlbf_mibf_prob_single_frame(double occupancy, unsigned hash_num, double freq, unsigned allowed_misses);
+int btlbf_interleave_mates(const char* seq1, const uint64_t* starts1, const char* seq2, const uint64_t* starts2,
+                           uint64_t n_pairs, char* out, uint64_t* out_starts, int mem, int device, void* stream);
+int btlbf_mibf_classify_tally(const btlbf_mibf_hit* hits, const uint32_t* n_hits, const uint32_t* sat_count,
+                              const uint32_t* eval_count, uint64_t n_rows, uint32_t max_results, uint64_t n_ids,
+                              uint64_t* best, uint64_t* any, uint64_t* totals6, int mem, int device, void* stream);
+
 /* ---- multi-GPU hash-range sharding ------------------------------------------------
  * The M-bit filter is cut into n_shards contiguous bit ranges; shard g (btlbf_create_shard) holds
  * positions [g*M/n, (g+1)*M/n).  Routing is by POSITION, so the concatenated shard bodies are the
@@ -589,7 +627,12 @@ int btlbf_count_per_seq(const uint64_t* hit_bits, const uint64_t* valid_bits, ui
 enum btlbf_fastx_flags {
 	BTLBF_FASTX_RECORDS = 0,  /* the wrapped lines of a FASTA record form ONE sequence (contigsToBloom) */
 	BTLBF_FASTX_LINES = 1,    /* every sequence line is its own sequence (loadBf) */
-	BTLBF_FASTX_PAGEABLE = 2  /* do not pin the host buffers */
+	BTLBF_FASTX_PAGEABLE = 2, /* do not pin the host buffers */
+	BTLBF_FASTX_WHOLE = 4     /* never cut a sequence: one that does not fit the rest of a batch opens the next batch, and
+	                             one longer than a whole batch is an error (EINVAL from btlbf_fastx_next, the message
+	                             names the record).  batch_bytes may then be as small as the longest sequence.  An empty
+	                             sequence line of a FASTQ record is delivered as an empty sequence (without the flag it
+	                             is skipped), so that sequences and records correspond one to one */
 };
 typedef struct btlbf_fastx btlbf_fastx;
 
@@ -626,6 +669,50 @@ int btlbf_insert_fastx(btlbf_filter* f, const char* path, uint32_t flags, uint64
                        btlbf_fastx_stats* stats);
 int btlbf_contains_fastx(btlbf_filter* f, const char* path, uint32_t flags, uint64_t batch_bytes,
                          btlbf_fastx_stats* stats);
+
+/* ---- read classification from FASTA / FASTQ files ---------------------------------------------------------
+ * What a caller of the reference writes around MIBFQuerySupport<T>::query (MIBFQuerySupport.hpp:95-130): read the
+ * file(s), classify every read or pair, keep per-read results and reads per id.  Three modes:
+ *   path2 == NULL, no flag            : single reads (mibf_classify_seqs); a row is a record;
+ *   path2 != NULL                     : record i of path1 and record i of path2 are pair i (mibf_classify_pairs);
+ *   path2 == NULL, CLASSIFY_INTERLEAVED: records 2i and 2i + 1 of path1 are pair i.
+ * path2 together with the flag is EINVAL.  flags may also hold BTLBF_FASTX_LINES / BTLBF_FASTX_PAGEABLE;
+ * BTLBF_FASTX_WHOLE is always set: a row is a whole read, so batch_bytes (0 = 64 MiB) must hold the longest record.
+ * Rows come out in file order, and equal mibf_classify_seqs / _pairs on the same reads row for row.
+ * open : checks, before any HIP call and before the miBF is looked at: null arguments (path2 may be null), max_results == 0,
+ *   n_ids == 0, both pairing modes, an unreadable file (EIO); then n_ids against the id type as mibf_classify_seqs.  The
+ *   tables are uploaded once.  Each file gets one sequential parser (btlbf_fastx_open / _next) on a thread of its own --
+ *   at most two threads, no byte-range readers -- that fills pinned batches ahead of the caller, a bounded number in
+ *   flight; the two files' batches are cut by bytes and zipped on the host record by record (csrc/mibf_zip.hpp).
+ * next : one batch: the bases and offsets go to the device on a copy stream; on the compute stream, for two files,
+ *   interleave_mates, then mibf_classify_seqs / _pairs (BTLBF_DEVICE), mibf_classify_tally into the handle's running
+ *   device totals, and the copy of the four result arrays into one of two pinned result sets.  mibf_classify_* plans
+ *   on the host and synchronises its stream, so the call returns with its batch finished; the parser threads parse the
+ *   next two batches meanwhile.  *first_row is contiguous from 0 over successive calls; *n_rows == 0 at end of input.
+ *   The result pointers stay valid until the call after the next one (btlbf_fastx_next's rule).  hits may be passed as
+ *   NULL together with the other three result pointers: no per-row result then leaves the device (the whole-file call
+ *   does this).  A FASTQ record with an empty sequence line is a row (an empty read, or an empty mate); a FASTA record
+ *   without sequence lines is not.  Whatever classify reports (an id index >= n_ids,
+ *   ENOMEM for a row beyond the scratch budget) and whatever the parser reports (a record longer than a batch) comes
+ *   back unchanged.  Unequal record counts of the two files, or an odd count in interleaved mode, are EFORMAT from the
+ *   call that reaches the end of input; rows delivered before stay delivered.
+ * tally : the running totals so far, in the layout of mibf_classify_tally (best / any: n_ids entries).
+ * classify_fastx : open, next until the end without per-row copies, tally, close.  stats (optional): n_records,
+ *   n_bases, n_batches, seconds_parse (the slower parser), seconds_total; n_windows / n_hits stay 0. */
+enum { BTLBF_CLASSIFY_INTERLEAVED = 1u << 8 };
+typedef struct btlbf_mibf_fastx btlbf_mibf_fastx;
+int btlbf_mibf_classify_fastx_open(btlbf_mibf_fastx** c, btlbf_mibf* m, const char* path1, const char* path2,
+                                   uint32_t flags, const btlbf_mibf_classify_params* p, const double* per_frame_prob,
+                                   const uint32_t* min_count_per_id, uint64_t n_ids, uint64_t batch_bytes);
+int btlbf_mibf_classify_fastx_next(btlbf_mibf_fastx* c, uint64_t* first_row, uint64_t* n_rows,
+                                   const btlbf_mibf_hit** hits, const uint32_t** n_hits, const uint32_t** sat_count,
+                                   const uint32_t** eval_count);
+int btlbf_mibf_classify_fastx_tally(btlbf_mibf_fastx* c, uint64_t* best, uint64_t* any, uint64_t* totals6);
+void btlbf_mibf_classify_fastx_close(btlbf_mibf_fastx* c);
+int btlbf_mibf_classify_fastx(btlbf_mibf* m, const char* path1, const char* path2, uint32_t flags,
+                              const btlbf_mibf_classify_params* p, const double* per_frame_prob,
+                              const uint32_t* min_count_per_id, uint64_t n_ids, uint64_t batch_bytes, uint64_t* best,
+                              uint64_t* any, uint64_t* totals6, btlbf_fastx_stats* stats);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,8 @@
 // The paired overload query(itr1, itr2, minCount) (one walk over both mates' frames in turn) is here
 //   * queryPairs(seqs1, seqs2, minCount) for a whole batch of pairs in one call (btlbf_mibf_classify_pairs), and
 //   * query(seq1, seq2, minCount), the per-pair call, again one GPU round trip each.
+// Whole files: queryFile / queryFiles / queryInterleavedFile stream FASTA / FASTQ input through the same classification and
+// hand the rows to a callback in file order; summarizeFile returns reads per id only (btlbf_mibf_classify_fastx_*).
 // getSatCount() / getEvalCount() answer for the last query(seq) or query(seq1, seq2); the batched queries return them
 // per read or pair.  The rules for what the reference leaves open are in include/btlbf.h (btlbf_mibf_classify_seqs).
 // Errors follow detail.hpp.
@@ -110,6 +112,64 @@ class MIBFQuerySupport
 		return m_signifResults;
 	}
 
+	// The reads of FASTA / FASTQ files (plain or gzip), classified in file order, batch by batch
+	// (btlbf_mibf_classify_fastx_*): queryFile -- every record on its own; queryFiles -- record i of path1 and record i
+	// of path2 as pair i; queryInterleavedFile -- records 2i and 2i + 1 of one file as pair i.  Per batch
+	// sink(firstRow, results, satCounts, evalCounts) is called with the batch's rows (results[r]: at most maxResults
+	// records of row firstRow + r; the vectors are the callee's until it returns); a functor passed as an lvalue keeps
+	// its state.  Returns the number of rows.
+	// batchBytes: bases per batch (0: 64 MiB); a record longer than that is an error.
+	template<typename Sink>
+	uint64_t queryFile(const std::string& path, const std::vector<unsigned>& minCount, Sink&& sink, uint64_t batchBytes = 0) const
+	{
+		return classifyFile(path.c_str(), nullptr, 0, minCount, sink, batchBytes);
+	}
+	template<typename Sink>
+	uint64_t queryFiles(const std::string& path1, const std::string& path2, const std::vector<unsigned>& minCount, Sink&& sink,
+	                    uint64_t batchBytes = 0) const
+	{
+		return classifyFile(path1.c_str(), path2.c_str(), 0, minCount, sink, batchBytes);
+	}
+	template<typename Sink>
+	uint64_t queryInterleavedFile(const std::string& path, const std::vector<unsigned>& minCount, Sink&& sink,
+	                              uint64_t batchBytes = 0) const
+	{
+		return classifyFile(path.c_str(), nullptr, BTLBF_CLASSIFY_INTERLEAVED, minCount, sink, batchBytes);
+	}
+
+	// reads (or pairs) per id over whole files, no per-read result leaves the GPU (btlbf_mibf_classify_fastx)
+	struct FileSummary
+	{
+		std::vector<uint64_t> best; // per id: rows whose first result is this id
+		std::vector<uint64_t> any;  // per id: rows with this id among their first maxResults results
+		uint64_t rows, rowsWithoutResult, rowsWithSeveral, rowsTruncated, satCount, evalCount;
+	};
+	// path2 empty: single reads, or with `interleaved` the pairs of one file
+	FileSummary summarizeFile(const std::string& path1, const std::string& path2, const std::vector<unsigned>& minCount,
+	                          bool interleaved = false, uint64_t batchBytes = 0) const
+	{
+		std::vector<uint32_t> mc(minCount.begin(), minCount.end());
+		if (mc.size() != m_perFrameProb.size())
+			btlbf_shim::check(BTLBF_EINVAL);
+		FileSummary out;
+		out.best.assign(mc.size() + 1, 0);
+		out.any.assign(mc.size() + 1, 0);
+		uint64_t t[6] = {0, 0, 0, 0, 0, 0};
+		btlbf_shim::check(btlbf_mibf_classify_fastx(m_miBF.handle(), path1.c_str(), path2.empty() ? nullptr : path2.c_str(),
+		                                            interleaved ? (uint32_t)BTLBF_CLASSIFY_INTERLEAVED : 0u, &m_par,
+		                                            m_perFrameProb.data(), mc.data(), mc.size(), batchBytes, &out.best[0],
+		                                            &out.any[0], t, nullptr));
+		out.best.resize(mc.size());
+		out.any.resize(mc.size());
+		out.rows = t[0];
+		out.rowsWithoutResult = t[1];
+		out.rowsWithSeveral = t[2];
+		out.rowsTruncated = t[3];
+		out.satCount = t[4];
+		out.evalCount = t[5];
+		return out;
+	}
+
 	unsigned getSatCount() const { return m_satCount; }
 	unsigned getEvalCount() const { return m_evalCount; }
 
@@ -148,6 +208,49 @@ class MIBFQuerySupport
 			}
 		}
 		return out;
+	}
+
+	struct FileHandle // closes on every way out of classifyFile, a throwing sink included
+	{
+		btlbf_mibf_fastx* c;
+		FileHandle() : c(nullptr) {}
+		~FileHandle() { btlbf_mibf_classify_fastx_close(c); }
+	};
+
+	template<typename Sink>
+	uint64_t classifyFile(const char* path1, const char* path2, uint32_t flags, const std::vector<unsigned>& minCount,
+	                      Sink& sink, uint64_t batchBytes) const
+	{
+		std::vector<uint32_t> mc(minCount.begin(), minCount.end());
+		if (mc.size() != m_perFrameProb.size())
+			btlbf_shim::check(BTLBF_EINVAL);
+		FileHandle fh;
+		btlbf_shim::check(btlbf_mibf_classify_fastx_open(&fh.c, m_miBF.handle(), path1, path2, flags, &m_par,
+		                                                 m_perFrameProb.data(), mc.data(), mc.size(), batchBytes));
+		const size_t mr = m_par.max_results;
+		uint64_t rows = 0;
+		for (;;) {
+			uint64_t first = 0, n = 0;
+			const btlbf_mibf_hit* hits = nullptr;
+			const uint32_t *nHits = nullptr, *sat = nullptr, *ev = nullptr;
+			btlbf_shim::check(btlbf_mibf_classify_fastx_next(fh.c, &first, &n, &hits, &nHits, &sat, &ev));
+			if (n == 0)
+				break;
+			std::vector<std::vector<QueryResult> > results(n);
+			for (uint64_t s = 0; s < n; ++s) {
+				const size_t w = nHits[s] < mr ? nHits[s] : mr;
+				for (size_t i = 0; i < w; ++i) {
+					const btlbf_mibf_hit& h = hits[s * mr + i];
+					QueryResult r = {(T)h.id,           h.count,           h.nonSatCount, h.totalCount,
+					                 h.totalNonSatCount, h.nonSatFrameCount, h.solidCount,  m_perFrameProb[h.id]};
+					results[s].push_back(r);
+				}
+			}
+			std::vector<uint32_t> satCounts(sat, sat + n), evalCounts(ev, ev + n);
+			sink(first, results, satCounts, evalCounts);
+			rows += n;
+		}
+		return rows;
 	}
 
 	const MIBloomFilter<T>& m_miBF;

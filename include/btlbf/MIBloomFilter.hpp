@@ -3,6 +3,7 @@
 // lives in MI355X HBM and every call forwards to the HIP kernels.  T is uint16_t or uint32_t.
 //   * construction: from a stage-1 bit filter (MIBloomFilter(hashNum, k, bv, seeds), :122-147) or from a data file
 //     plus that filter (MIBloomFilter(path), :149-248; the bit vector is not read from a .sdsl file).
+//   * calcFrameProbs / calcProbSingleFrame as in the reference (the perFrameProb table of MIBFQuerySupport).
 //   * batch members instead of per-k-mer iterators: insertIDs (insertMIBF), insertSaturation, query
 //     (getMatchSignature) over sequence buffers with a layout and one id per sequence.
 // Errors follow detail.hpp (message + exit(1), or std::runtime_error with BTLBF_SHIM_THROW).
@@ -53,6 +54,24 @@ class MIBloomFilter
 		for (size_t i = 0; i < c.size(); ++i)
 			counts[i] += c[i];
 		return sat;
+	}
+
+	// calcProbSingleFrame (MIBloomFilter.hpp:65-77), computed by the library in the reference's order of operations
+	static inline double calcProbSingleFrame(double occupancy, unsigned hashNum, double freq, unsigned allowedMisses)
+	{
+		return btlbf_mibf_prob_single_frame(occupancy, hashNum, freq, allowedMisses);
+	}
+
+	// calcFrameProbs (MIBloomFilter.hpp:664-679): frameProbs is preallocated to the number of ids + 1; entries 1.. are
+	// written, entry 0 is left as it is; returns the proportion of saturated entries.  Where the reference has undefined
+	// behaviour (an id in the array beyond frameProbs, allowedMiss above the hash count, no entry with an id) this is an
+	// error (btlbf_mibf_frame_probs).
+	double calcFrameProbs(std::vector<double>& frameProbs, unsigned allowedMiss) const
+	{
+		double satProp = 0.0;
+		btlbf_shim::check(btlbf_mibf_frame_probs(m_m, allowedMiss, frameProbs.empty() ? nullptr : &frameProbs[0],
+		                                         frameProbs.size(), &satProp));
+		return satProp;
 	}
 
 	// the whole ID array (getData of every rank)
