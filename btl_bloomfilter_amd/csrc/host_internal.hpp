@@ -1,5 +1,5 @@
 // csrc/host_internal.hpp -- what the host units of the C ABI share, and only that: error plumbing, the filter object,
-// its cached device scratch (DevScratch) and its lazy-clear protocol, the staging pool and the mailbox, parameter
+// its cached device scratch (DevScratch, PinScratch) and its lazy-clear protocol, the staging pool and the mailbox, parameter
 // blocks, sequence views, and the entry of the sequence path into the partitioned pipeline.  Defined in: capi.cpp
 // (errors, clear protocol, dev_pool, mailbox, parameter blocks, make_filter, views), host_seq.cpp (seq_precheck),
 // host_partition.cpp (the pipeline; its planner's types are private to it), host_aux.cpp (rank_build).  fastx.cpp uses
@@ -18,20 +18,36 @@ int btlbf_set_error(int code, const char* fmt, ...) __attribute__((format(printf
 
 namespace btlbf {
 
-// A device buffer the filter keeps between calls: hipMalloc / hipFree of tens of GB cost more than the kernels, so it
-// only ever grows, and btlbf_release_scratch and btlbf_destroy give it back.  The caller has the device selected.
-struct DevScratch {
+// A device buffer its owner keeps between calls (DevScratch): hipMalloc / hipFree of tens of GB cost more than the
+// kernels, so it only ever grows; release() (btlbf_release_scratch, btlbf_destroy) or the owner's end give it back.  Its
+// pinned sibling (PinScratch) is what the host and a stream hand each other.  The caller has the device selected.
+template <bool kPinned>
+struct GrowOnly {
 	void* p = nullptr;
 	uint64_t bytes = 0;
+	GrowOnly() = default;
+	GrowOnly(const GrowOnly&) = delete;
+	GrowOnly& operator=(const GrowOnly&) = delete;
+	~GrowOnly() { release(); }
 	// room for `need` bytes (the contents are not kept); false = there is none, and the buffer is then empty
 	bool grow(uint64_t need, int device);
+	// ... with a quarter to spare, so that a slightly larger batch of a file does not allocate again
+	bool keep_room(uint64_t need, int device) { return need <= bytes || grow(need + need / 4, device); }
 	void release()
 	{
-		(void)hipFree(p); // synchronises with work in flight
+		if (p)
+			(void)(kPinned ? hipHostFree(p) : hipFree(p)); // synchronises with work in flight
 		p = nullptr;
 		bytes = 0;
 	}
+	template <class T>
+	T* as() const
+	{
+		return static_cast<T*>(p);
+	}
 };
+using DevScratch = GrowOnly<false>;
+using PinScratch = GrowOnly<true>;
 
 } // namespace btlbf
 
@@ -260,15 +276,17 @@ struct DevPool {
 };
 DevPool& dev_pool(); // the one pool of the process (capi.cpp)
 
-inline bool DevScratch::grow(uint64_t need, int device)
+template <bool kPinned>
+bool GrowOnly<kPinned>::grow(uint64_t need, int device)
 {
 	if (need <= bytes)
 		return true;
 	release();
-	if (hipMalloc(&p, need) != hipSuccess) { // parked staging buffers of HOST-mode calls may be what is missing
+	const auto alloc = [&] { return kPinned ? hipHostMalloc(&p, need, hipHostMallocDefault) : hipMalloc(&p, need); };
+	if (alloc() != hipSuccess) { // parked staging buffers of HOST-mode calls may be what is missing
 		(void)hipGetLastError();
 		dev_pool().drain(device);
-		if (hipMalloc(&p, need) != hipSuccess) {
+		if (alloc() != hipSuccess) {
 			(void)hipGetLastError();
 			p = nullptr;
 			return false;
@@ -376,13 +394,14 @@ SeqArgs base_args(const btlbf_filter* f, const SeqView& v, uint64_t len);
 int seq_precheck(const btlbf_filter* f); // host_seq.cpp
 inline uint64_t bitmap_bytes(uint64_t len) { return (len + 63) / 64 * 8; }
 
-// copy a device bitmap / array back to the caller when the call was BTLBF_HOST
+// device view of an array of the caller's that the call writes: a pooled buffer when the call was BTLBF_HOST, copied back
+// by finish() (copy_in: the call updates the array, so the caller's contents go in first)
 struct OutBuf {
 	DevBuf dev;
 	void* host = nullptr;
 	size_t n = 0;
 	void* d = nullptr;
-	int prepare(void* user, size_t nbytes, int mem, bool zero, hipStream_t s)
+	int prepare(void* user, size_t nbytes, int mem, bool zero, hipStream_t s, bool copy_in = false)
 	{
 		n = nbytes;
 		if (!user)
@@ -393,6 +412,8 @@ struct OutBuf {
 			host = user;
 			HIP_TRY(dev.alloc_pooled(nbytes));
 			d = dev.p;
+			if (copy_in && nbytes)
+				HIP_TRY(hipMemcpyAsync(d, user, nbytes, hipMemcpyHostToDevice, s));
 		}
 		if (zero && nbytes)
 			HIP_TRY(hipMemsetAsync(d, 0, nbytes, s));
@@ -403,6 +424,24 @@ struct OutBuf {
 		if (host && n)
 			HIP_TRY(hipMemcpyAsync(host, d, n, hipMemcpyDeviceToHost, s));
 		return BTLBF_OK;
+	}
+	template <class T>
+	T* as() const
+	{
+		return static_cast<T*>(d);
+	}
+};
+
+// ... and of a read-only array: copied in, never back
+struct InBuf : private OutBuf {
+	int prepare(const void* user, size_t nbytes, int mem, hipStream_t s)
+	{
+		return OutBuf::prepare(const_cast<void*>(user), nbytes, mem, false, s, true);
+	}
+	template <class T>
+	const T* as() const
+	{
+		return static_cast<const T*>(d);
 	}
 };
 
@@ -419,10 +458,43 @@ int split_contains(btlbf_filter* f, const SeqArgs& a, int direct_op, hipStream_t
 hipError_t rank_build(const btlbf_filter* f, uint64_t** d_il, uint64_t* n_blocks, uint64_t* ones);
 
 // What the other miBF host units (host_mibf_probs.cpp, host_mibf_fastx.cpp) need of the object, which host_mibf.cpp keeps
-// to itself: its device, its id width, and the largest m_counts index over the data array -- the reduction classify caches
-// until the array next changes.
+// to itself: its device, its id width, the largest m_counts index over the data array -- the reduction classify caches
+// until the array next changes -- and the classification of sequences that are on the device already.
 int mibf_device(const btlbf_mibf* m);
 unsigned mibf_id_bytes(const btlbf_mibf* m);
 int mibf_max_id(btlbf_mibf* m, uint64_t* max_id);
+
+// The offsets of a plan's batches on the device, every batch's rebased to its first byte (to the kernels a batch is a
+// buffer of its own).  A plan of one batch is the whole call and uses the call's own device offsets where it has them;
+// otherwise the offsets of all batches go up in one copy from pinned memory, before the first batch runs: batch i,
+// sequences [s0, s1), has its s1 - s0 + 1 entries from entry s0 + i on.  The owner synchronises the stream before it goes.
+struct MibfBatchStarts {
+	PinScratch host;
+	DevScratch dev;
+	const uint64_t* d = nullptr; // batch i of the plan, sq in sequences: layout(q, sq, i)
+	// per_unit: the sequences of a unit of the plan (2: pairs); d_call: the call's n_seqs + 1 offsets on the device, or null
+	int stage(const MibfSeqs& q, const MibfPlan& plan, unsigned per_unit, const uint64_t* d_call, int device, hipStream_t s);
+	LayoutParams layout(const MibfSeqs& q, const MibfBatch& sq, size_t i) const
+	{
+		return LayoutParams{q.read_len ? nullptr : d + sq.s0 + i, sq.s1 - sq.s0, q.read_len};
+	}
+};
+
+// mibf_classify_device's scratch: phase 1's values, bitmaps and hit masks of the largest batch, the lists and tables of
+// the sequences whose table does not fit LDS, the batches' offsets.  kept: a file's handle owns it (hence keep_room)
+struct MibfClassifyScratch {
+	DevScratch vals, hit, valid, masks, big_list, big_off, big_tab;
+	MibfBatchStarts starts;
+	bool kept = false;
+	bool reserve(const MibfPlan& plan, unsigned h, unsigned id_bytes, int device);
+};
+
+// MIBFQuerySupport<T>::query of the sequences q (or, with `pairs`, of the pairs 2i, 2i + 1) of d_seq[0, len), everything
+// on the device: the tables of n_ids entries, the four result arrays of a row per unit; d_starts: q's offsets, where the
+// caller has them there.  Takes the miBF's lock, plans under its budget, returns with `s` synchronised (host_mibf.cpp).
+int mibf_classify_device(btlbf_mibf* m, const uint8_t* d_seq, uint64_t len, const MibfSeqs& q, const uint64_t* d_starts,
+                         const btlbf_mibf_classify_params& p, const double* d_prob, const uint32_t* d_minc, uint64_t n_ids,
+                         btlbf_mibf_hit* d_hits, uint32_t* d_n, uint32_t* d_sat, uint32_t* d_eval, bool pairs, hipStream_t s,
+                         MibfClassifyScratch& sc);
 
 } // namespace btlbf

@@ -1,6 +1,9 @@
 // csrc/host_mibf.cpp -- the multi-index Bloom filter (miBF stages 2-4): the ID array over the rank structure of a bit
-// filter: create, insert IDs, saturate, query, statistics, files (kernels: mibf_kernels.hip; the rank structure itself
-// is built by rank_build, host_aux.cpp).
+// filter: create, insert IDs, saturate, query, classify, statistics, files (kernels: mibf_kernels.hip,
+// mibf_classify_kernels.hip, mibf_classify_pair_kernels.hip; the rank structure itself is built by rank_build,
+// host_aux.cpp).  Classification has two halves: mibf_classify_device works on device-resident sequences, from their host
+// offsets and with scratch its caller owns (host_mibf_fastx.cpp calls it per batch); btlbf_mibf_classify_seqs / _pairs add
+// what the C ABI owes any caller: the argument checks, a HOST-mode call's staging, a DEVICE-mode caller's offsets read back.
 #include "../../include/btlbf.h"
 #include "internal.hpp"
 #include "host_internal.hpp"
@@ -128,8 +131,7 @@ int mibf_make(btlbf_mibf** out, btlbf_filter* f, unsigned id_bytes, const std::v
 // the sequences of one call: device buffer, the sequence boundaries on the host (batches are cut on them), ids
 struct MibfCall {
 	SeqView v;
-	DevBuf ids_buf;
-	const uint32_t* d_ids = nullptr;
+	InBuf ids;
 	MibfSeqs q;
 };
 
@@ -160,32 +162,7 @@ int mibf_prepare(MibfCall& c, const char* seq, uint64_t len, const btlbf_layout*
 		q.read_len = layout->read_len;
 		q.n_seqs = len / q.read_len;
 	}
-	c.d_ids = ids;
-	if (want_ids && mem != BTLBF_DEVICE) {
-		HIP_TRY(c.ids_buf.alloc((q.n_seqs + 1) * 4));
-		if (q.n_seqs)
-			HIP_TRY(hipMemcpyAsync(c.ids_buf.p, ids, q.n_seqs * 4, hipMemcpyHostToDevice, s));
-		c.d_ids = c.ids_buf.as<uint32_t>();
-	}
-	return BTLBF_OK;
-}
-
-// the sequences of a batch as a buffer of their own: the layout's starts rebased to the batch's first byte
-int mibf_batch_layout(const MibfSeqs& q, const MibfBatch& b, DevBuf& starts_buf, LayoutParams& lay, hipStream_t s)
-{
-	lay.starts = nullptr;
-	lay.n_seqs = b.s1 - b.s0;
-	lay.read_len = q.read_len;
-	if (q.read_len)
-		return BTLBF_OK;
-	std::vector<uint64_t> rb(b.s1 - b.s0 + 1);
-	for (uint64_t i = b.s0; i <= b.s1; ++i)
-		rb[i - b.s0] = q.starts[i] - q.starts[b.s0];
-	HIP_TRY(starts_buf.alloc(rb.size() * 8));
-	HIP_TRY(hipMemcpyAsync(starts_buf.p, rb.data(), rb.size() * 8, hipMemcpyHostToDevice, s));
-	HIP_TRY(hipStreamSynchronize(s)); // rb is freed on return
-	lay.starts = starts_buf.as<uint64_t>();
-	return BTLBF_OK;
+	return want_ids ? c.ids.prepare(ids, q.n_seqs * 4, mem, s) : BTLBF_OK;
 }
 
 // a plan that failed: no batch has run, so the ID array, the counts and the caller's outputs are as they were
@@ -270,6 +247,33 @@ int btlbf::mibf_max_id(btlbf_mibf* m, uint64_t* max_id)
 	return rc;
 }
 
+int btlbf::MibfBatchStarts::stage(const MibfSeqs& q, const MibfPlan& plan, unsigned per_unit, const uint64_t* d_call,
+                                  int device, hipStream_t s)
+{
+	d = d_call;
+	if (q.read_len || (plan.batches.size() == 1 && d_call))
+		return BTLBF_OK;
+	const uint64_t n = q.n_seqs + plan.batches.size();
+	if (!host.grow(n * 8, device) || !dev.grow(n * 8, device))
+		return fail(BTLBF_ENOMEM, "miBF: the batches' offsets of %llu sequences", (unsigned long long)q.n_seqs);
+	uint64_t* o = host.as<uint64_t>();
+	for (const MibfBatch& b : plan.batches)
+		for (uint64_t i = per_unit * b.s0; i <= per_unit * b.s1; ++i)
+			*o++ = q.starts[i] - q.starts[per_unit * b.s0];
+	HIP_TRY(hipMemcpyAsync(dev.p, host.p, (o - host.as<uint64_t>()) * 8, hipMemcpyHostToDevice, s));
+	d = dev.as<uint64_t>();
+	return BTLBF_OK;
+}
+
+bool btlbf::MibfClassifyScratch::reserve(const MibfPlan& plan, unsigned h, unsigned id_bytes, int device)
+{
+	// never an empty buffer: a batch of empty sequences still hands the kernels pointers
+	auto room = [&](DevScratch& b, uint64_t n) { return kept ? b.keep_room(n + 16, device) : b.grow(n + 16, device); };
+	return room(vals, plan.max_bytes * h * id_bytes) && room(hit, bitmap_bytes(plan.max_bytes)) &&
+	       room(valid, bitmap_bytes(plan.max_bytes)) && room(masks, plan.max_bytes) && room(big_list, plan.max_big * 4) &&
+	       room(big_off, plan.max_big * 8) && room(big_tab, plan.max_slots * kMibfClsSlotWords * 4);
+}
+
 extern "C" int btlbf_mibf_create(btlbf_mibf** out, btlbf_filter* f, unsigned id_bytes)
 {
 	if (!out || !f)
@@ -336,13 +340,12 @@ extern "C" int btlbf_mibf_insert_ids_seqs(btlbf_mibf* m, const char* seq, uint64
 		(void)hipGetLastError();
 		return fail(BTLBF_ENOMEM, "miBF: %llu bytes of insert scratch", (unsigned long long)(cap * 32 + temp_bytes));
 	}
+	MibfBatchStarts starts;
+	if ((rc = starts.stage(c.q, plan, 1, c.v.lay.starts, m->device, s)))
+		return rc;
 	for (const MibfBatch& b : plan.batches) {
 		const uint64_t b0 = c.q.start(b.s0), blen = c.q.start(b.s1) - b0, n = blen * m->h;
-		DevBuf sb;
-		LayoutParams lay;
-		if ((rc = mibf_batch_layout(c.q, b, sb, lay, s)))
-			return rc;
-		MibfArgs a = mibf_args(m, c.v.d_seq + b0, blen, lay);
+		MibfArgs a = mibf_args(m, c.v.d_seq + b0, blen, starts.layout(c.q, b, &b - plan.batches.data()));
 		a.seq_bits = std::max(1u, bit_len(b.s1 - b.s0 - 1));
 		const unsigned end_bit = bit_len(m->pop) + a.seq_bits;
 		if (end_bit > 64)
@@ -353,7 +356,7 @@ extern "C" int btlbf_mibf_insert_ids_seqs(btlbf_mibf* m, const char* seq, uint64
 		HIP_TRY(launch_mibf_seq(MIBF_EMIT, m->id_bytes, a, s));
 		HIP_TRY(mibf_sort_pairs(temp.p, temp_bytes, kin.as<uint64_t>(), kout.as<uint64_t>(), vin.as<uint64_t>(),
 		                        vout.as<uint64_t>(), n, end_bit, s));
-		HIP_TRY(launch_mibf_insert_apply(m->id_bytes, kout.as<uint64_t>(), vout.as<uint64_t>(), n, a.seq_bits, c.d_ids, b.s0,
+		HIP_TRY(launch_mibf_insert_apply(m->id_bytes, kout.as<uint64_t>(), vout.as<uint64_t>(), n, a.seq_bits, c.ids.as<uint32_t>(), b.s0,
 		                                 m->d_data, m->d_counts, s));
 	}
 	HIP_TRY(hipStreamSynchronize(s)); // scratch is freed on return
@@ -388,12 +391,12 @@ extern "C" int btlbf_mibf_saturate_seqs(btlbf_mibf* m, const char* seq, uint64_t
 			(void)hipGetLastError();
 			return fail(BTLBF_ENOMEM, "miBF: serial saturation scratch");
 		}
+		MibfBatchStarts starts;
+		if ((rc = starts.stage(c.q, plan, 1, c.v.lay.starts, m->device, s)))
+			return rc;
 		for (const MibfBatch& b : plan.batches) {
 			const uint64_t b0 = c.q.start(b.s0), blen = c.q.start(b.s1) - b0;
-			DevBuf sb;
-			LayoutParams lay;
-			if ((rc = mibf_batch_layout(c.q, b, sb, lay, s)))
-				return rc;
+			const LayoutParams lay = starts.layout(c.q, b, &b - plan.batches.data());
 			SeqArgs h{};
 			h.seq = c.v.d_seq + b0;
 			h.len = blen;
@@ -405,7 +408,7 @@ extern "C" int btlbf_mibf_saturate_seqs(btlbf_mibf* m, const char* seq, uint64_t
 			h.valid_bits = valid.as<uint8_t>();
 			HIP_TRY(launch_seq_op(OP_HASH_ONLY, h, s));
 			HIP_TRY(launch_mibf_serial_saturate(m->id_bytes, rows.as<uint64_t>(), valid.as<uint64_t>(), blen, m->h, m->mod,
-			                                    m->d_il, lay, c.d_ids, b.s0, m->d_data, m->d_counts, &m->d_stat->clean, s));
+			                                    m->d_il, lay, c.ids.as<uint32_t>(), b.s0, m->d_data, m->d_counts, &m->d_stat->clean, s));
 		}
 	} else if (len) {
 		// decisions against the snapshot: mutations (rank, window) 16 bytes + 16 more for their sort, saturated ranks 8
@@ -418,7 +421,7 @@ extern "C" int btlbf_mibf_saturate_seqs(btlbf_mibf* m, const char* seq, uint64_t
 		}
 		HIP_TRY(hipMemsetAsync(cnt.p, 0, 16, s));
 		MibfArgs a = mibf_args(m, c.v.d_seq, len, c.v.lay);
-		a.ids = c.d_ids;
+		a.ids = c.ids.as<uint32_t>();
 		a.keys = kin.as<uint64_t>();
 		a.vals = vin.as<uint64_t>();
 		a.sat = sat.as<uint64_t>();
@@ -444,7 +447,7 @@ extern "C" int btlbf_mibf_saturate_seqs(btlbf_mibf* m, const char* seq, uint64_t
 		HIP_TRY(mibf_sort_pairs(temp.p, temp_bytes, kin.as<uint64_t>(), kout.as<uint64_t>(), vin.as<uint64_t>(),
 		                        vout.as<uint64_t>(), n_out[0], bit_len(m->pop), s));
 		HIP_TRY(launch_mibf_mutate_apply(m->id_bytes, kout.as<uint64_t>(), vout.as<uint64_t>(), n_out[0], c.v.lay,
-		                                 c.d_ids, m->d_data, m->d_counts, s));
+		                                 c.ids.as<uint32_t>(), m->d_data, m->d_counts, s));
 		HIP_TRY(launch_mibf_saturate(m->id_bytes, sat.as<uint64_t>(), n_out[1], m->d_data, s));
 	}
 	uint64_t st[kMibfCallStat / 8];
@@ -493,6 +496,93 @@ extern "C" int btlbf_mibf_query_seqs(btlbf_mibf* m, const char* seq, uint64_t le
 // sequences 2i, 2i + 1 (:111-130): phase 1 is the MIBF_QUERY launch of btlbf_mibf_query_seqs into scratch, over the
 // sequence layout either way; phase 2 the walk of mibf_classify_kernels.hip / mibf_classify_pair_kernels.hip, batch by
 // batch under the budget.  A unit (a result row, an entry of the plan) is a sequence or a pair.
+int btlbf::mibf_classify_device(btlbf_mibf* m, const uint8_t* d_seq, uint64_t len, const MibfSeqs& q, const uint64_t* d_starts,
+                                const btlbf_mibf_classify_params& p, const double* d_prob, const uint32_t* d_minc,
+                                uint64_t n_ids, btlbf_mibf_hit* d_hits, uint32_t* d_n, uint32_t* d_sat, uint32_t* d_eval,
+                                bool pairs, hipStream_t s, MibfClassifyScratch& sc)
+{
+	std::lock_guard<std::mutex> lk(m->mu);
+	DeviceGuard g(m->device);
+	m->cls_paths[0] = m->cls_paths[1] = 0;
+	const uint64_t n_units = pairs ? q.n_seqs / 2 : q.n_seqs, per = pairs ? 2 : 1;
+	if (n_units == 0)
+		return BTLBF_OK;
+	if (q.start(per * n_units) > len)
+		return fail(BTLBF_EINVAL, "internal error: miBF classify: offsets beyond the %llu bytes", (unsigned long long)len);
+	// every index the walk will use lies inside the caller's tables
+	int rc = mibf_max_id_locked(m, s);
+	if (rc)
+		return rc;
+	if (m->max_id >= n_ids)
+		return fail(BTLBF_EINVAL, "miBF classify: the ID array holds id %llu, the tables %llu entries; nothing was written",
+		            (unsigned long long)m->max_id, (unsigned long long)n_ids);
+	const MibfPlan plan = pairs ? mibf_plan_classify_pairs(q, mibf_budget(m->budget), m->k, m->h, m->id_bytes, n_ids)
+	                            : mibf_plan_classify(q, mibf_budget(m->budget), m->k, m->h, m->id_bytes, n_ids);
+	if (!plan.ok())
+		return mibf_too_big(plan, pairs ? "pair" : "sequence");
+	if (!sc.reserve(plan, m->h, m->id_bytes, m->device))
+		return fail(BTLBF_ENOMEM, "miBF classify: scratch of %llu bytes", (unsigned long long)mibf_budget(m->budget));
+	if ((rc = sc.starts.stage(q, plan, per, d_starts, m->device, s)))
+		return rc;
+	HIP_TRY(hipMemsetAsync(d_hits, 0, n_units * p.max_results * sizeof(btlbf_mibf_hit), s));
+	HIP_TRY(hipMemsetAsync(d_n, 0, n_units * 4, s));
+	HIP_TRY(hipMemsetAsync(d_sat, 0, n_units * 4, s));
+	HIP_TRY(hipMemsetAsync(d_eval, 0, n_units * 4, s));
+	HIP_TRY(hipMemsetAsync(m->d_stat, 0, kMibfCallStat, s));
+	HIP_TRY(hipMemsetAsync(m->d_stat->cls_paths, 0, sizeof(MibfStat::cls_paths), s));
+	uint64_t big0 = 0; // the batch's first entry of the plan's big lists
+	for (size_t i = 0; i < plan.batches.size(); ++i) {
+		const MibfBatch& b = plan.batches[i];
+		const MibfBatch sq{per * b.s0, per * b.s1, b.big, b.slots}; // the batch in sequences: a plan of pairs counts pairs
+		const uint64_t b0 = q.start(sq.s0), blen = q.start(sq.s1) - b0;
+		const LayoutParams lay = sc.starts.layout(q, sq, i);
+		if (blen)
+			HIP_TRY(launch_mibf_seq(MIBF_QUERY, m->id_bytes,
+			                        mibf_query_args(m, d_seq + b0, blen, lay, p.max_miss, sc.vals.p, sc.hit.p, sc.valid.p,
+			                                        sc.masks.p), s));
+		MibfClassifyArgs a{};
+		a.values = sc.vals.p;
+		a.valid_bits = sc.valid.as<uint64_t>();
+		a.match_bits = sc.hit.as<uint64_t>();
+		a.hit_masks = sc.masks.as<uint8_t>();
+		a.layout = lay;
+		a.h = m->h;
+		a.k = m->k;
+		a.spaced = m->hp.n_seeds ? 1 : 0;
+		a.extra_frame_limit = p.extra_frame_limit;
+		a.min_count = p.min_count;
+		a.best_hit_agree = p.best_hit_agree;
+		a.max_results = p.max_results;
+		a.extra_count = p.extra_count;
+		a.per_frame_prob = d_prob;
+		a.min_count_per_id = d_minc;
+		a.n_ids = n_ids;
+		a.hits = d_hits;
+		a.n_hits = d_n;
+		a.sat_count = d_sat;
+		a.eval_count = d_eval;
+		a.row0 = b.s0;
+		a.stat = m->d_stat->cls_paths;
+		if (b.big) {
+			HIP_TRY(hipMemcpyAsync(sc.big_list.p, &plan.big_seq[big0], b.big * 4, hipMemcpyHostToDevice, s));
+			HIP_TRY(hipMemcpyAsync(sc.big_off.p, &plan.big_off[big0], b.big * 8, hipMemcpyHostToDevice, s));
+			HIP_TRY(hipStreamSynchronize(s)); // an early return frees the plan
+			big0 += b.big;
+			a.big_list = sc.big_list.as<uint32_t>();
+			a.big_off = sc.big_off.as<uint64_t>();
+			a.big_tab = sc.big_tab.as<uint32_t>();
+			a.n_big = b.big;
+		}
+		HIP_TRY(pairs ? launch_mibf_classify_pairs(m->id_bytes, a, s) : launch_mibf_classify(m->id_bytes, a, s));
+	}
+	unsigned long long paths[2] = {0, 0};
+	HIP_TRY(hipMemcpyAsync(paths, m->d_stat->cls_paths, sizeof paths, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s)); // d_stat is reused by the next call, and the scratch may go with the caller
+	memcpy(m->cls_paths, paths, sizeof paths);
+	return BTLBF_OK;
+}
+
+// the C entry points' half: the checks, the staging and read-back of mibf_prepare, tables and results of a HOST-mode call
 static int mibf_classify(btlbf_mibf* m, const char* seq, uint64_t len, const btlbf_layout* layout,
                          const btlbf_mibf_classify_params* p, const double* per_frame_prob,
                          const uint32_t* min_count_per_id, uint64_t n_ids, btlbf_mibf_hit* hits, uint32_t* n_hits,
@@ -511,103 +601,27 @@ static int mibf_classify(btlbf_mibf* m, const char* seq, uint64_t len, const btl
 	if (n_ids > (1ull << (m->id_bytes * 8 - 1)))
 		return fail(BTLBF_EINVAL, "miBF classify: n_ids must be 1..2^%u for %u-byte ids, not %llu", m->id_bytes * 8 - 1,
 		            m->id_bytes, (unsigned long long)n_ids);
-	std::lock_guard<std::mutex> lk(m->mu);
 	DeviceGuard g(m->device);
 	hipStream_t s = static_cast<hipStream_t>(stream);
 	MibfCall c;
 	int rc = mibf_prepare(c, seq, len, layout, nullptr, mem, s, false);
 	if (rc)
 		return rc;
-	m->cls_paths[0] = m->cls_paths[1] = 0;
 	const uint64_t n_units = pairs ? c.q.n_seqs / 2 : c.q.n_seqs;
-	if (n_units == 0)
-		return BTLBF_OK;
-	// every index the walk will use lies inside the caller's tables
-	if ((rc = mibf_max_id_locked(m, s)))
-		return rc;
-	if (m->max_id >= n_ids)
-		return fail(BTLBF_EINVAL, "miBF classify: the ID array holds id %llu, the tables %llu entries; nothing was written",
-		            (unsigned long long)m->max_id, (unsigned long long)n_ids);
-	const MibfPlan plan = pairs ? mibf_plan_classify_pairs(c.q, mibf_budget(m->budget), m->k, m->h, m->id_bytes, n_ids)
-	                            : mibf_plan_classify(c.q, mibf_budget(m->budget), m->k, m->h, m->id_bytes, n_ids);
-	if (!plan.ok())
-		return mibf_too_big(plan, pairs ? "pair" : "sequence");
-	DevBuf vals, hit, valid, masks, big_list, big_off, big_tab, tables;
-	if (vals.alloc(plan.max_bytes * m->h * m->id_bytes) || hit.alloc(bitmap_bytes(plan.max_bytes)) ||
-	    valid.alloc(bitmap_bytes(plan.max_bytes)) || masks.alloc(plan.max_bytes) || big_list.alloc(plan.max_big * 4) ||
-	    big_off.alloc(plan.max_big * 8) || big_tab.alloc(plan.max_slots * kMibfClsSlotWords * 4)) {
-		(void)hipGetLastError();
-		return fail(BTLBF_ENOMEM, "miBF classify: scratch of %llu bytes", (unsigned long long)mibf_budget(m->budget));
-	}
-	const double* d_prob = per_frame_prob;
-	const uint32_t* d_minc = min_count_per_id;
-	if (mem != BTLBF_DEVICE) {
-		HIP_TRY(tables.alloc(n_ids * 12));
-		HIP_TRY(hipMemcpyAsync(tables.p, per_frame_prob, n_ids * 8, hipMemcpyHostToDevice, s));
-		HIP_TRY(hipMemcpyAsync(tables.as<uint8_t>() + n_ids * 8, min_count_per_id, n_ids * 4, hipMemcpyHostToDevice, s));
-		d_prob = tables.as<double>();
-		d_minc = reinterpret_cast<const uint32_t*>(tables.as<uint8_t>() + n_ids * 8);
-	}
+	InBuf prob, minc;
 	OutBuf o_hits, o_n, o_sat, o_eval;
-	if ((rc = o_hits.prepare(hits, n_units * p->max_results * sizeof(btlbf_mibf_hit), mem, true, s)) ||
-	    (rc = o_n.prepare(n_hits, n_units * 4, mem, true, s)) || (rc = o_sat.prepare(sat_count, n_units * 4, mem, true, s)) ||
-	    (rc = o_eval.prepare(eval_count, n_units * 4, mem, true, s)))
+	if ((rc = prob.prepare(per_frame_prob, n_ids * 8, mem, s)) || (rc = minc.prepare(min_count_per_id, n_ids * 4, mem, s)) ||
+	    (rc = o_hits.prepare(hits, n_units * p->max_results * sizeof(btlbf_mibf_hit), mem, false, s)) ||
+	    (rc = o_n.prepare(n_hits, n_units * 4, mem, false, s)) || (rc = o_sat.prepare(sat_count, n_units * 4, mem, false, s)) ||
+	    (rc = o_eval.prepare(eval_count, n_units * 4, mem, false, s)))
 		return rc;
-	HIP_TRY(hipMemsetAsync(m->d_stat, 0, kMibfCallStat, s));
-	HIP_TRY(hipMemsetAsync(m->d_stat->cls_paths, 0, sizeof(MibfStat::cls_paths), s));
-	uint64_t big0 = 0; // the batch's first entry of the plan's big lists
-	for (const MibfBatch& b : plan.batches) {
-		// the batch in sequences: a plan of pairs counts pairs
-		const MibfBatch sq{pairs ? 2 * b.s0 : b.s0, pairs ? 2 * b.s1 : b.s1, b.big, b.slots};
-		const uint64_t b0 = c.q.start(sq.s0), blen = c.q.start(sq.s1) - b0;
-		DevBuf sb;
-		LayoutParams lay;
-		if ((rc = mibf_batch_layout(c.q, sq, sb, lay, s)))
-			return rc;
-		if (blen)
-			HIP_TRY(launch_mibf_seq(MIBF_QUERY, m->id_bytes,
-			                        mibf_query_args(m, c.v.d_seq + b0, blen, lay, p->max_miss, vals.p, hit.p, valid.p, masks.p), s));
-		MibfClassifyArgs q{};
-		q.values = vals.p;
-		q.valid_bits = valid.as<uint64_t>();
-		q.match_bits = hit.as<uint64_t>();
-		q.hit_masks = masks.as<uint8_t>();
-		q.layout = lay;
-		q.h = m->h;
-		q.k = m->k;
-		q.spaced = m->hp.n_seeds ? 1 : 0;
-		q.extra_frame_limit = p->extra_frame_limit;
-		q.min_count = p->min_count;
-		q.best_hit_agree = p->best_hit_agree;
-		q.max_results = p->max_results;
-		q.extra_count = p->extra_count;
-		q.per_frame_prob = d_prob;
-		q.min_count_per_id = d_minc;
-		q.n_ids = n_ids;
-		q.hits = o_hits.d;
-		q.n_hits = static_cast<uint32_t*>(o_n.d);
-		q.sat_count = static_cast<uint32_t*>(o_sat.d);
-		q.eval_count = static_cast<uint32_t*>(o_eval.d);
-		q.row0 = b.s0;
-		q.stat = m->d_stat->cls_paths;
-		if (b.big) {
-			HIP_TRY(hipMemcpyAsync(big_list.p, &plan.big_seq[big0], b.big * 4, hipMemcpyHostToDevice, s));
-			HIP_TRY(hipMemcpyAsync(big_off.p, &plan.big_off[big0], b.big * 8, hipMemcpyHostToDevice, s));
-			HIP_TRY(hipStreamSynchronize(s)); // an early return frees the plan
-			big0 += b.big;
-			q.big_list = big_list.as<uint32_t>();
-			q.big_off = big_off.as<uint64_t>();
-			q.big_tab = big_tab.as<uint32_t>();
-			q.n_big = b.big;
-		}
-		HIP_TRY(pairs ? launch_mibf_classify_pairs(m->id_bytes, q, s) : launch_mibf_classify(m->id_bytes, q, s));
-	}
-	unsigned long long paths[2] = {0, 0};
-	HIP_TRY(hipMemcpyAsync(paths, m->d_stat->cls_paths, sizeof paths, hipMemcpyDeviceToHost, s));
-	if ((rc = o_hits.finish(s)) || (rc = o_n.finish(s)) || (rc = o_sat.finish(s)) || (rc = o_eval.finish(s)))
+	MibfClassifyScratch sc;
+	if ((rc = mibf_classify_device(m, c.v.d_seq, len, c.q, c.v.lay.starts, *p, prob.as<double>(), minc.as<uint32_t>(), n_ids,
+	                               o_hits.as<btlbf_mibf_hit>(), o_n.as<uint32_t>(), o_sat.as<uint32_t>(),
+	                               o_eval.as<uint32_t>(), pairs, s, sc)) ||
+	    (rc = o_hits.finish(s)) || (rc = o_n.finish(s)) || (rc = o_sat.finish(s)) || (rc = o_eval.finish(s)))
 		return rc;
-	HIP_TRY(hipStreamSynchronize(s)); // scratch is freed on return
-	memcpy(m->cls_paths, paths, sizeof paths);
+	HIP_TRY(hipStreamSynchronize(s)); // the staging buffers go back to the pool on return
 	return BTLBF_OK;
 }
 

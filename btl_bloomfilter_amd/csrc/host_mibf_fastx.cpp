@@ -5,10 +5,11 @@
 // byte-range readers of run_fastx, which deliver in arrival order, are not used), filling the parser's two pinned
 // batches ahead of the caller.  btlbf_mibf_classify_fastx_next takes the next batch -- for two files the next run of
 // pairs the zipper of mibf_zip.hpp forms from the two sides' current batches --, copies it to the device on the copy
-// stream and runs, on the compute stream: interleave_mates (two files), btlbf_mibf_classify_seqs / _pairs with
-// BTLBF_DEVICE, the tally kernel into the handle's running totals, and the copy of the four result arrays into one of
-// two pinned result sets.  btlbf_mibf_classify_* plans its batches on the host and synchronises its stream, so `next`
-// returns with batch j finished; what overlaps the GPU is the parsing of batches j + 1 and j + 2 on the parser threads.
+// stream and runs, on the compute stream: interleave_mates (two files), mibf_classify_device (host_mibf.cpp) with the
+// batch's host offsets (those stage_side wrote; for two files their closed form, mibf_zip_starts) and the handle's own
+// scratch, the tally kernel into the handle's running totals, and the copy of the four result arrays into one of two
+// pinned result sets.  mibf_classify_device plans its batches on the host and synchronises its stream, so `next` returns
+// with batch j finished; what overlaps the GPU is the parsing of batches j + 1 and j + 2 on the parser threads.
 #include "../../include/btlbf.h"
 #include "internal.hpp"
 #include "host_internal.hpp"
@@ -36,34 +37,6 @@ double now_s()
 	return duration<double>(steady_clock::now().time_since_epoch()).count();
 }
 
-// a memory space's view of the arrays of a HOST-mode helper call: staged in, and the outputs copied back
-struct Staged {
-	DevBuf buf;
-	void* host = nullptr;
-	size_t n = 0;
-	void* d = nullptr;
-	int in(const void* user, size_t nbytes, int mem, bool copy, hipStream_t s)
-	{
-		n = nbytes;
-		if (mem == BTLBF_DEVICE) {
-			d = const_cast<void*>(user);
-			return BTLBF_OK;
-		}
-		host = const_cast<void*>(user);
-		HIP_TRY(buf.alloc_pooled(nbytes));
-		d = buf.p;
-		if (copy && nbytes)
-			HIP_TRY(hipMemcpyAsync(d, user, nbytes, hipMemcpyHostToDevice, s));
-		return BTLBF_OK;
-	}
-	int out(hipStream_t s)
-	{
-		if (host && n)
-			HIP_TRY(hipMemcpyAsync(host, d, n, hipMemcpyDeviceToHost, s));
-		return BTLBF_OK;
-	}
-};
-
 } // namespace
 
 extern "C" int btlbf_interleave_mates(const char* seq1, const uint64_t* starts1, const char* seq2, const uint64_t* starts2,
@@ -84,17 +57,17 @@ extern "C" int btlbf_interleave_mates(const char* seq1, const uint64_t* starts1,
 	for (uint64_t i = 0; i < n_pairs; ++i)
 		if (starts1[i + 1] < starts1[i] || starts2[i + 1] < starts2[i])
 			return btlbf_set_error(BTLBF_EINVAL, "starts must not decrease");
-	Staged a, sa, b, sb, o, so;
+	InBuf a, sa, b, sb;
+	OutBuf o, so;
 	int rc;
-	if ((rc = a.in(seq1, starts1[n_pairs], mem, true, s)) || (rc = sa.in(starts1, (n_pairs + 1) * 8, mem, true, s)) ||
-	    (rc = b.in(seq2, starts2[n_pairs], mem, true, s)) || (rc = sb.in(starts2, (n_pairs + 1) * 8, mem, true, s)) ||
-	    (rc = o.in(out, starts1[0] + starts2[0] + n1 + n2, mem, false, s)) ||
-	    (rc = so.in(out_starts, (2 * n_pairs + 1) * 8, mem, false, s)))
+	if ((rc = a.prepare(seq1, starts1[n_pairs], mem, s)) || (rc = sa.prepare(starts1, (n_pairs + 1) * 8, mem, s)) ||
+	    (rc = b.prepare(seq2, starts2[n_pairs], mem, s)) || (rc = sb.prepare(starts2, (n_pairs + 1) * 8, mem, s)) ||
+	    (rc = o.prepare(out, starts1[0] + starts2[0] + n1 + n2, mem, false, s)) ||
+	    (rc = so.prepare(out_starts, (2 * n_pairs + 1) * 8, mem, false, s)))
 		return rc;
-	HIP_TRY(launch_interleave_mates(static_cast<const uint8_t*>(a.d), static_cast<const uint64_t*>(sa.d),
-	                                static_cast<const uint8_t*>(b.d), static_cast<const uint64_t*>(sb.d), n_pairs,
-	                                static_cast<uint8_t*>(o.d), static_cast<uint64_t*>(so.d), s));
-	if ((rc = o.out(s)) || (rc = so.out(s)))
+	HIP_TRY(launch_interleave_mates(a.as<uint8_t>(), sa.as<uint64_t>(), b.as<uint8_t>(), sb.as<uint64_t>(), n_pairs,
+	                                o.as<uint8_t>(), so.as<uint64_t>(), s));
+	if ((rc = o.finish(s)) || (rc = so.finish(s)))
 		return rc;
 	HIP_TRY(hipStreamSynchronize(s));
 	return BTLBF_OK;
@@ -112,20 +85,19 @@ extern "C" int btlbf_mibf_classify_tally(const btlbf_mibf_hit* hits, const uint3
 	if (!g.ok)
 		return fail(BTLBF_EHIP, "no GPU %d: this library has no CPU path", device);
 	hipStream_t s = static_cast<hipStream_t>(stream);
-	Staged h, n, sa, ev, b, a, t;
+	InBuf h, n, sa, ev;
+	OutBuf b, a, t; // updated: the caller's counts go in first
 	int rc;
-	if ((rc = h.in(hits, n_rows * max_results * sizeof(btlbf_mibf_hit), mem, true, s)) ||
-	    (rc = n.in(n_hits, n_rows * 4, mem, true, s)) || (rc = sa.in(sat_count, n_rows * 4, mem, true, s)) ||
-	    (rc = ev.in(eval_count, n_rows * 4, mem, true, s)) || (rc = b.in(best, n_ids * 8, mem, true, s)) ||
-	    (rc = a.in(any, n_ids * 8, mem, true, s)) || (rc = t.in(totals6, 6 * 8, mem, true, s)))
+	if ((rc = h.prepare(hits, n_rows * max_results * sizeof(btlbf_mibf_hit), mem, s)) ||
+	    (rc = n.prepare(n_hits, n_rows * 4, mem, s)) || (rc = sa.prepare(sat_count, n_rows * 4, mem, s)) ||
+	    (rc = ev.prepare(eval_count, n_rows * 4, mem, s)) || (rc = b.prepare(best, n_ids * 8, mem, false, s, true)) ||
+	    (rc = a.prepare(any, n_ids * 8, mem, false, s, true)) || (rc = t.prepare(totals6, 6 * 8, mem, false, s, true)))
 		return rc;
-	HIP_TRY(launch_mibf_tally(h.d, static_cast<const uint32_t*>(n.d), static_cast<const uint32_t*>(sa.d),
-	                          static_cast<const uint32_t*>(ev.d), n_rows, max_results, n_ids,
-	                          static_cast<unsigned long long*>(b.d), static_cast<unsigned long long*>(a.d),
-	                          static_cast<unsigned long long*>(t.d), s));
+	HIP_TRY(launch_mibf_tally(h.as<void>(), n.as<uint32_t>(), sa.as<uint32_t>(), ev.as<uint32_t>(), n_rows, max_results, n_ids,
+	                          b.as<unsigned long long>(), a.as<unsigned long long>(), t.as<unsigned long long>(), s));
 	if (mem == BTLBF_DEVICE)
 		return BTLBF_OK;
-	if ((rc = b.out(s)) || (rc = a.out(s)) || (rc = t.out(s)))
+	if ((rc = b.finish(s)) || (rc = a.finish(s)) || (rc = t.finish(s)))
 		return rc;
 	HIP_TRY(hipStreamSynchronize(s));
 	return BTLBF_OK;
@@ -219,38 +191,6 @@ struct Side {
 	}
 };
 
-// pinned or device memory that only grows
-struct Grow {
-	void* p = nullptr;
-	uint64_t bytes = 0;
-	bool pinned = false;
-	hipError_t need(uint64_t n)
-	{
-		if (n <= bytes)
-			return hipSuccess;
-		release();
-		n += n / 4;
-		const hipError_t e = pinned ? hipHostMalloc(&p, n, hipHostMallocDefault) : hipMalloc(&p, n);
-		if (e == hipSuccess)
-			bytes = n;
-		else
-			p = nullptr;
-		return e;
-	}
-	void release()
-	{
-		if (p)
-			(void)(pinned ? hipHostFree(p) : hipFree(p));
-		p = nullptr;
-		bytes = 0;
-	}
-	template <class T>
-	T* as() const
-	{
-		return static_cast<T*>(p);
-	}
-};
-
 } // namespace
 
 struct btlbf_mibf_fastx {
@@ -263,13 +203,12 @@ struct btlbf_mibf_fastx {
 	MibfZip zip;
 	HostBatch cur[2];
 	hipStream_t copy_s = nullptr, comp_s = nullptr;
-	// device: the tables, the batch (bases and starts per side, the interleaved buffer), the results, the totals
-	double* d_prob = nullptr;
-	uint32_t* d_minc = nullptr;
-	Grow d_bases[2], d_starts[2], d_out, d_out_starts, d_hits, d_n, d_sat, d_eval;
-	unsigned long long* d_tot = nullptr; // best[n_ids], any[n_ids], totals[6]
-	// pinned: starts rebased to the batch, the rest of an odd interleaved batch, two result sets
-	Grow h_starts[2], h_left, h_hits[2], h_n[2], h_sat[2], h_eval[2];
+	// grow only, free themselves.  Device: the tables, the totals (best[n_ids], any[n_ids], totals[6]), the batch (bases and
+	// starts per side, the interleaved buffer), the results; pinned: the sides' starts, an odd batch's rest, two result sets
+	DevScratch d_prob, d_minc, d_tot, d_bases[2], d_starts[2], d_out, d_out_starts, d_hits, d_n, d_sat, d_eval;
+	PinScratch h_starts[2], h_left, h_hits[2], h_n[2], h_sat[2], h_eval[2];
+	MibfClassifyScratch scratch;
+	MibfSeqs seqs; // the batch's sequences for the planner: the host offsets
 	uint64_t left_len = 0;
 	bool has_left = false;
 	int res = 0;
@@ -279,32 +218,20 @@ struct btlbf_mibf_fastx {
 	std::string end_err;
 	uint64_t n_batches = 0, n_bases = 0;
 
-	btlbf_mibf_fastx()
-	{
-		for (Grow* g : {&h_starts[0], &h_starts[1], &h_left, &h_hits[0], &h_hits[1], &h_n[0], &h_n[1], &h_sat[0], &h_sat[1],
-		                &h_eval[0], &h_eval[1]})
-			g->pinned = true;
-	}
-	~btlbf_mibf_fastx()
+	btlbf_mibf_fastx() { scratch.kept = true; }
+	~btlbf_mibf_fastx() // the buffers go after this: none while work is pending
 	{
 		side[0].stop();
 		side[1].stop();
-		if (comp_s)
-			(void)hipStreamSynchronize(comp_s);
-		if (copy_s)
-			(void)hipStreamSynchronize(copy_s);
-		for (Grow* g : {&d_bases[0], &d_bases[1], &d_starts[0], &d_starts[1], &d_out, &d_out_starts, &d_hits, &d_n, &d_sat,
-		                &d_eval, &h_starts[0], &h_starts[1], &h_left, &h_hits[0], &h_hits[1], &h_n[0], &h_n[1], &h_sat[0],
-		                &h_sat[1], &h_eval[0], &h_eval[1]})
-			g->release();
-		(void)hipFree(d_prob);
-		(void)hipFree(d_minc);
-		(void)hipFree(d_tot);
-		if (copy_s)
-			(void)hipStreamDestroy(copy_s);
-		if (comp_s)
-			(void)hipStreamDestroy(comp_s);
+		for (hipStream_t s : {comp_s, copy_s})
+			if (s) {
+				(void)hipStreamSynchronize(s);
+				(void)hipStreamDestroy(s);
+			}
 	}
+	template <class Buf>
+	bool room(Buf& b, uint64_t n) { return b.keep_room(n, device); }
+	unsigned long long* tot() const { return d_tot.as<unsigned long long>(); }
 };
 
 namespace {
@@ -326,38 +253,30 @@ int end_input(btlbf_mibf_fastx* c, int rc)
 	return rc;
 }
 
-// One batch on the device: n_rows rows over the sequences of `seq` (layout `starts`, n_seqs sequences): classify, tally,
-// and -- for a caller who wants rows -- the copies into the pinned result set `c->res`
-int run_batch(btlbf_mibf_fastx* c, const char* seq, uint64_t len, const uint64_t* starts, uint64_t n_seqs, uint64_t n_rows,
-              bool want_rows)
+// One batch on the device: n_rows rows over the sequences of d_seq[0, len), whose offsets are c->seqs.starts and, on the
+// device, d_starts: classify, tally, and -- for a caller who wants rows -- the copies into the pinned result set `c->res`
+int run_batch(btlbf_mibf_fastx* c, const void* d_seq, uint64_t len, const void* d_starts, uint64_t n_rows, bool want_rows)
 {
-	const uint64_t mr = c->par.max_results;
-	if (c->d_hits.need(n_rows * mr * sizeof(btlbf_mibf_hit)) || c->d_n.need(n_rows * 4) || c->d_sat.need(n_rows * 4) ||
-	    c->d_eval.need(n_rows * 4)) {
-		(void)hipGetLastError();
+	const uint64_t hit_bytes = n_rows * c->par.max_results * sizeof(btlbf_mibf_hit);
+	c->seqs.n_seqs = c->seqs.starts.size() - 1;
+	if (!c->room(c->d_hits, hit_bytes) || !c->room(c->d_n, n_rows * 4) || !c->room(c->d_sat, n_rows * 4) ||
+	    !c->room(c->d_eval, n_rows * 4))
 		return fail(BTLBF_ENOMEM, "miBF classify file: results of %llu rows", (unsigned long long)n_rows);
-	}
-	btlbf_layout lay;
-	lay.starts = starts;
-	lay.n_seqs = n_seqs;
-	lay.read_len = 0;
-	const int rc = (c->pairs ? btlbf_mibf_classify_pairs : btlbf_mibf_classify_seqs)(
-	    c->m, seq, len, &lay, &c->par, c->d_prob, c->d_minc, c->n_ids, c->d_hits.as<btlbf_mibf_hit>(), c->d_n.as<uint32_t>(),
-	    c->d_sat.as<uint32_t>(), c->d_eval.as<uint32_t>(), BTLBF_DEVICE, c->comp_s);
+	const int rc = mibf_classify_device(c->m, static_cast<const uint8_t*>(d_seq), len, c->seqs,
+	                                    static_cast<const uint64_t*>(d_starts), c->par, c->d_prob.as<double>(),
+	                                    c->d_minc.as<uint32_t>(), c->n_ids, c->d_hits.as<btlbf_mibf_hit>(),
+	                                    c->d_n.as<uint32_t>(), c->d_sat.as<uint32_t>(), c->d_eval.as<uint32_t>(), c->pairs,
+	                                    c->comp_s, c->scratch);
 	if (rc)
 		return rc;
 	HIP_TRY(launch_mibf_tally(c->d_hits.p, c->d_n.as<uint32_t>(), c->d_sat.as<uint32_t>(), c->d_eval.as<uint32_t>(), n_rows,
-	                          c->par.max_results, c->n_ids, c->d_tot, c->d_tot + c->n_ids, c->d_tot + 2 * c->n_ids,
-	                          c->comp_s));
+	                          c->par.max_results, c->n_ids, c->tot(), c->tot() + c->n_ids, c->tot() + 2 * c->n_ids, c->comp_s));
 	if (want_rows) {
 		const int s = c->res;
-		if (c->h_hits[s].need(n_rows * mr * sizeof(btlbf_mibf_hit)) || c->h_n[s].need(n_rows * 4) ||
-		    c->h_sat[s].need(n_rows * 4) || c->h_eval[s].need(n_rows * 4)) {
-			(void)hipGetLastError();
+		if (!c->room(c->h_hits[s], hit_bytes) || !c->room(c->h_n[s], n_rows * 4) || !c->room(c->h_sat[s], n_rows * 4) ||
+		    !c->room(c->h_eval[s], n_rows * 4))
 			return fail(BTLBF_ENOMEM, "miBF classify file: pinned results of %llu rows", (unsigned long long)n_rows);
-		}
-		HIP_TRY(hipMemcpyAsync(c->h_hits[s].p, c->d_hits.p, n_rows * mr * sizeof(btlbf_mibf_hit), hipMemcpyDeviceToHost,
-		                       c->comp_s));
+		HIP_TRY(hipMemcpyAsync(c->h_hits[s].p, c->d_hits.p, hit_bytes, hipMemcpyDeviceToHost, c->comp_s));
 		HIP_TRY(hipMemcpyAsync(c->h_n[s].p, c->d_n.p, n_rows * 4, hipMemcpyDeviceToHost, c->comp_s));
 		HIP_TRY(hipMemcpyAsync(c->h_sat[s].p, c->d_sat.p, n_rows * 4, hipMemcpyDeviceToHost, c->comp_s));
 		HIP_TRY(hipMemcpyAsync(c->h_eval[s].p, c->d_eval.p, n_rows * 4, hipMemcpyDeviceToHost, c->comp_s));
@@ -375,11 +294,9 @@ int stage_side(btlbf_mibf_fastx* c, int sd, const HostBatch& b, uint64_t a, uint
                uint64_t* len_out)
 {
 	const uint64_t b0 = b.starts[a], len = b.starts[a + n] - b0, extra = lead ? 1 : 0;
-	if (c->d_bases[sd].need(lead_len + len + 64) || c->d_starts[sd].need((n + extra + 1) * 8) ||
-	    c->h_starts[sd].need((n + extra + 1) * 8)) {
-		(void)hipGetLastError();
+	if (!c->room(c->d_bases[sd], lead_len + len + 64) || !c->room(c->d_starts[sd], (n + extra + 1) * 8) ||
+	    !c->room(c->h_starts[sd], (n + extra + 1) * 8))
 		return fail(BTLBF_ENOMEM, "miBF classify file: a batch of %llu bytes", (unsigned long long)(lead_len + len));
-	}
 	uint64_t* hs = c->h_starts[sd].as<uint64_t>();
 	hs[0] = 0;
 	for (uint64_t i = 0; i <= n; ++i)
@@ -418,17 +335,15 @@ int next_rows(btlbf_mibf_fastx* c, uint64_t* n_rows, bool want_rows)
 		if ((rc = stage_side(c, 0, c->cur[0], a0, n, false, 0, &l0)) ||
 		    (rc = stage_side(c, 1, c->cur[1], a1, n, false, 0, &l1)))
 			return rc;
-		if (c->d_out.need(l0 + l1 + 64) || c->d_out_starts.need((2 * n + 1) * 8)) {
-			(void)hipGetLastError();
+		if (!c->room(c->d_out, l0 + l1 + 64) || !c->room(c->d_out_starts, (2 * n + 1) * 8))
 			return fail(BTLBF_ENOMEM, "miBF classify file: a batch of %llu bytes", (unsigned long long)(l0 + l1));
-		}
-		// the batch is on the device before the compute stream reads it (classify reads the offsets back on the host, too)
-		HIP_TRY(hipStreamSynchronize(c->copy_s));
+		HIP_TRY(hipStreamSynchronize(c->copy_s)); // the batch is on the device before the compute stream reads it
+		// the kernels read the interleaved offsets on the device; the planner gets the same on the host
 		HIP_TRY(launch_interleave_mates(c->d_bases[0].as<uint8_t>(), c->d_starts[0].as<uint64_t>(), c->d_bases[1].as<uint8_t>(),
 		                                c->d_starts[1].as<uint64_t>(), n, c->d_out.as<uint8_t>(),
 		                                c->d_out_starts.as<uint64_t>(), c->comp_s));
-		HIP_TRY(hipStreamSynchronize(c->comp_s));
-		if ((rc = run_batch(c, c->d_out.as<char>(), l0 + l1, c->d_out_starts.as<uint64_t>(), 2 * n, n, want_rows)))
+		c->seqs.starts = mibf_zip_starts(c->h_starts[0].as<uint64_t>(), c->h_starts[1].as<uint64_t>(), n);
+		if ((rc = run_batch(c, c->d_out.p, l0 + l1, c->d_out_starts.p, n, want_rows)))
 			return rc;
 		*n_rows = n;
 		return BTLBF_OK;
@@ -456,10 +371,8 @@ int next_rows(btlbf_mibf_fastx* c, uint64_t* n_rows, bool want_rows)
 		c->has_left = false;
 		if (odd) {
 			const uint64_t l0 = b.starts[b.ns - 1], ll = b.starts[b.ns] - l0;
-			if (c->h_left.need(ll + 64)) {
-				(void)hipGetLastError();
+			if (!c->room(c->h_left, ll + 64))
 				return fail(BTLBF_ENOMEM, "miBF classify file: a record of %llu bytes", (unsigned long long)ll);
-			}
 			memcpy(c->h_left.p, b.bases + l0, ll);
 			c->left_len = ll;
 			c->has_left = true;
@@ -467,7 +380,8 @@ int next_rows(btlbf_mibf_fastx* c, uint64_t* n_rows, bool want_rows)
 		const uint64_t rows = c->pairs ? n_seqs / 2 : n_seqs;
 		if (rows == 0)
 			continue; // a batch of one record that waits for its mate
-		if ((rc = run_batch(c, c->d_bases[0].as<char>(), len, c->d_starts[0].as<uint64_t>(), n_seqs, rows, want_rows)))
+		c->seqs.starts.assign(c->h_starts[0].as<uint64_t>(), c->h_starts[0].as<uint64_t>() + n_seqs + 1);
+		if ((rc = run_batch(c, c->d_bases[0].p, len, c->d_starts[0].p, rows, want_rows)))
 			return rc;
 		*n_rows = rows;
 		return BTLBF_OK;
@@ -511,19 +425,19 @@ extern "C" int btlbf_mibf_classify_fastx_open(btlbf_mibf_fastx** out, btlbf_mibf
 	DeviceGuard g(c->device);
 	const uint32_t pf = (flags & (BTLBF_FASTX_LINES | BTLBF_FASTX_PAGEABLE)) | BTLBF_FASTX_WHOLE;
 	const uint32_t k = btlbf_mibf_kmer_size(m);
+	const uint64_t tot_bytes = (2 * n_ids + 6) * 8;
 	hipError_t e = hipSuccess;
 	// the parsers' pinned buffers need the device to be current
 	if ((rc = btlbf_fastx_open(&c->side[0].r, path1, pf, k, c->cap)) ||
 	    (path2 && (rc = btlbf_fastx_open(&c->side[1].r, path2, pf, k, c->cap))))
 		goto bad;
-	if ((e = hipStreamCreateWithFlags(&c->copy_s, hipStreamNonBlocking)) != hipSuccess ||
+	if (!c->d_prob.grow(n_ids * 8, c->device) || !c->d_minc.grow(n_ids * 4, c->device) || !c->d_tot.grow(tot_bytes, c->device))
+		e = hipErrorOutOfMemory;
+	if (e != hipSuccess || (e = hipStreamCreateWithFlags(&c->copy_s, hipStreamNonBlocking)) != hipSuccess ||
 	    (e = hipStreamCreateWithFlags(&c->comp_s, hipStreamNonBlocking)) != hipSuccess ||
-	    (e = hipMalloc(reinterpret_cast<void**>(&c->d_prob), n_ids * 8)) != hipSuccess ||
-	    (e = hipMalloc(reinterpret_cast<void**>(&c->d_minc), n_ids * 4)) != hipSuccess ||
-	    (e = hipMalloc(reinterpret_cast<void**>(&c->d_tot), (2 * n_ids + 6) * 8)) != hipSuccess ||
-	    (e = hipMemcpy(c->d_prob, per_frame_prob, n_ids * 8, hipMemcpyHostToDevice)) != hipSuccess ||
-	    (e = hipMemcpy(c->d_minc, min_count_per_id, n_ids * 4, hipMemcpyHostToDevice)) != hipSuccess ||
-	    (e = hipMemset(c->d_tot, 0, (2 * n_ids + 6) * 8)) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) {
+	    (e = hipMemcpy(c->d_prob.p, per_frame_prob, n_ids * 8, hipMemcpyHostToDevice)) != hipSuccess ||
+	    (e = hipMemcpy(c->d_minc.p, min_count_per_id, n_ids * 4, hipMemcpyHostToDevice)) != hipSuccess ||
+	    (e = hipMemset(c->d_tot.p, 0, tot_bytes)) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) {
 		rc = fail(BTLBF_EHIP, "miBF classify file: %s", hipGetErrorString(e));
 		goto bad;
 	}
@@ -572,9 +486,9 @@ extern "C" int btlbf_mibf_classify_fastx_tally(btlbf_mibf_fastx* c, uint64_t* be
 		return btlbf_set_error(BTLBF_EINVAL, "null argument");
 	DeviceGuard g(c->device);
 	HIP_TRY(hipStreamSynchronize(c->comp_s));
-	HIP_TRY(hipMemcpy(best, c->d_tot, c->n_ids * 8, hipMemcpyDeviceToHost));
-	HIP_TRY(hipMemcpy(any, c->d_tot + c->n_ids, c->n_ids * 8, hipMemcpyDeviceToHost));
-	HIP_TRY(hipMemcpy(totals6, c->d_tot + 2 * c->n_ids, 6 * 8, hipMemcpyDeviceToHost));
+	HIP_TRY(hipMemcpy(best, c->tot(), c->n_ids * 8, hipMemcpyDeviceToHost));
+	HIP_TRY(hipMemcpy(any, c->tot() + c->n_ids, c->n_ids * 8, hipMemcpyDeviceToHost));
+	HIP_TRY(hipMemcpy(totals6, c->tot() + 2 * c->n_ids, 6 * 8, hipMemcpyDeviceToHost));
 	return BTLBF_OK;
 }
 

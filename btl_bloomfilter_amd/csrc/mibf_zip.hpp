@@ -11,8 +11,23 @@
 // No record is dropped or reordered: pair i is record i of side 0 and record i of side 1.
 #pragma once
 #include <cstdint>
+#include <vector>
 
 namespace btlbf {
+
+// The offsets of the buffer in which n pairs are interleaved (mate 1 of pair 0, mate 2 of pair 0, mate 1 of pair 1, ...),
+// from the offsets of the two sides' buffers, s1[0..n] and s2[0..n]: what interleave_mates_kernel writes on the device,
+// in closed form.  A side's offsets need not start at 0 (a window of a batch); the result starts at s1[0] + s2[0].
+inline std::vector<uint64_t> mibf_zip_starts(const uint64_t* s1, const uint64_t* s2, uint64_t n)
+{
+	std::vector<uint64_t> out(2 * n + 1);
+	for (uint64_t i = 0; i < n; ++i) {
+		out[2 * i] = s1[i] + s2[i];
+		out[2 * i + 1] = s1[i + 1] + s2[i];
+	}
+	out[2 * n] = s1[n] + s2[n];
+	return out;
+}
 
 struct MibfZip {
 	enum Step { NEED_0 = 0, NEED_1 = 1, TAKE, END, UNEQUAL };

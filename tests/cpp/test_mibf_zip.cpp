@@ -2,12 +2,15 @@
 // side s is the number i) cut into batches at random -- batches of 0 records and of 1 record among them, and all of one
 // side delivered before the other side's first batch wherever the zipper's requests allow it -- must come out as the
 // pairs (i, i), in order, each once; equal totals end with END, unequal ones with UNEQUAL, and only after every pair that
-// exists has been taken.  Host only; built with -fsanitize=address,undefined by tests/test_mibf_zip_cpu.py.
+// exists has been taken.  And the closed form of the interleaved buffer's offsets (mibf_zip_starts) against the offsets
+// of the buffer built by appending the mates one by one.  Host only; built with -fsanitize=address,undefined by
+// tests/test_mibf_zip_cpu.py.
 #include "../../btl_bloomfilter_amd/csrc/mibf_zip.hpp"
 
 #include <cstdio>
 #include <cstdlib>
 #include <random>
+#include <utility>
 #include <vector>
 
 using btlbf::MibfZip;
@@ -89,9 +92,50 @@ static void run_case(std::mt19937_64& rng, uint64_t n0, uint64_t n1, uint64_t lo
 	}
 }
 
+// side offsets of n records of random lengths, empty records among them, from a first offset that is not 0
+static std::vector<uint64_t> side_starts(std::mt19937_64& rng, uint64_t n, uint64_t first)
+{
+	std::vector<uint64_t> s(n + 1, first);
+	for (uint64_t i = 0; i < n; ++i)
+		s[i + 1] = s[i] + (rng() % 3 == 0 ? 0 : rng() % 300);
+	return s;
+}
+
+// mibf_zip_starts against the interleaved buffer built mate by mate: its offsets, and which bytes lie between them
+static void zip_starts_case(std::mt19937_64& rng, uint64_t n, uint64_t first1, uint64_t first2)
+{
+	const std::vector<uint64_t> s1 = side_starts(rng, n, first1), s2 = side_starts(rng, n, first2);
+	// a side's buffer holds, at byte j of its window, (side, j): enough to tell where every byte of the result came from
+	std::vector<uint64_t> concat_starts{0};
+	std::vector<std::pair<int, uint64_t>> buf;
+	for (uint64_t i = 0; i < n; ++i)
+		for (int side = 0; side < 2; ++side) {
+			const std::vector<uint64_t>& s = side ? s2 : s1;
+			for (uint64_t j = s[i]; j < s[i + 1]; ++j)
+				buf.push_back({side, j});
+			concat_starts.push_back(buf.size());
+		}
+	const std::vector<uint64_t> got = btlbf::mibf_zip_starts(s1.data(), s2.data(), n);
+	CHECK(got.size() == 2 * n + 1 && concat_starts.size() == 2 * n + 1);
+	for (uint64_t j = 0; j <= 2 * n; ++j)
+		CHECK(got[j] == first1 + first2 + concat_starts[j]);
+	// sequence 2i is mate 1 of pair i, 2i + 1 its mate 2, byte for byte
+	for (uint64_t j = 0; j < 2 * n; ++j) {
+		const std::vector<uint64_t>& s = j & 1 ? s2 : s1;
+		CHECK(got[j + 1] - got[j] == s[j / 2 + 1] - s[j / 2]);
+		for (uint64_t b = got[j] - got[0]; b < got[j + 1] - got[0]; ++b)
+			CHECK(buf[b].first == (int)(j & 1) && buf[b].second == s[j / 2] + (b - (got[j] - got[0])));
+	}
+}
+
 int main()
 {
 	std::mt19937_64 rng(12345);
+	for (uint64_t n : {0, 1, 2, 63, 64, 65})
+		for (g_case = 100000; g_case < 100050; ++g_case) {
+			const bool window = g_case % 5 != 0; // most cases: offsets that do not start at 0
+			zip_starts_case(rng, n, window ? 1 + rng() % 100000 : 0, window ? 1 + rng() % 100000 : 0);
+		}
 	for (g_case = 0; g_case < 20000; ++g_case) {
 		const uint64_t n0 = rng() % 40;
 		const uint64_t n1 = g_case % 3 == 0 ? rng() % 40 : n0; // a third of the cases with (mostly) unequal totals

@@ -139,6 +139,39 @@ def test_batches_of_exactly_the_longest_read_and_one_batch(files, kind):
     assert collect(files.run(kind, p, 0), exp, 1) == len(exp[1])  # the default batch: everything at once
 
 
+def plan_cost(n, pair, k, h, id_bytes, n_ids):
+    """what a read, or a pair, of n bytes takes of the scratch budget: the cost of mibf_plan_classify / _pairs
+    (csrc/mibf_plan.hpp), the table of mibf_classify_cap slots included where it does not fit LDS"""
+    cap = 16
+    while cap <= min(max(n - k + 1, 0) * h, n_ids):
+        cap <<= 1
+    slots = cap if cap > 256 else 0
+    return n * (h * id_bytes + 2) + (128 if pair else 64) + slots * 24 + (12 if slots else 0)
+
+
+@pytest.mark.parametrize("kind", ["single", "two", "interleaved"])
+def test_a_file_batch_cut_into_plan_batches(files, kind):
+    """the whole file as one file batch under a scratch budget of 4096 bytes: the plan cuts it into at least four
+    batches, whose offsets are rebased and staged by the handle's scratch; rows and tally as under the default budget"""
+    c, p, budget = files.case, PARAMS[0], 4096
+    exp = files.mem["single" if kind == "single" else "pairs", p]
+    units = [r.size for r in files.reads] if kind == "single" else [a.size + b.size for a, b in c.pairs]
+    costs = [plan_cost(n, kind != "single", len(c.seeds[0]), c.h, c.id_bytes, c.n_ids) for n in units]
+    print(kind, "units", len(costs), "largest", max(costs), "sum", sum(costs))
+    assert max(costs) <= budget and sum(costs) >= 4 * budget  # every unit fits; four batches at the least
+    c.m.setScratchBudget(budget)
+    try:
+        it = files.run(kind, p, 0)
+        batches = list(it)
+        got = it.tally()
+        it.close()
+    finally:
+        c.m.setScratchBudget(0)
+    assert len(batches) == 1 and collect(iter(batches), exp) == len(exp[1]) == len(units)
+    for g, e in zip(got, tally_model(*exp, c.n_ids, MAX_RESULTS)):
+        assert g.dtype == np.uint64 and g.tolist() == e.tolist()
+
+
 @pytest.mark.parametrize("kind", ["single", "two", "interleaved"])
 def test_gzip_input(files, kind, tmp_path):
     p = PARAMS[1]
