@@ -13,6 +13,10 @@
 //     batch i+1 while batch i is copied and hashed
 // Hashing semantics are those of the kernels (a window is skipped unless all k bytes are ACGTU in
 // either case -- the reference iterator's rule, vendor/ntHashIterator.hpp:59-86).
+// A read error (an I/O error, a truncated or corrupt gzip stream) is BTLBF_EIO from the btlbf_fastx_next call that meets
+// it, never the end of the input.
+// Environment: BTLBF_FASTX_THREADS (parser threads), BTLBF_FASTX_MT_MIN_BYTES (smallest file parsed by several threads),
+// BTLBF_FASTX_DEV_BYTES (tests: the size of a device batch, so that small files run the two-slot rotation).
 #include "host_internal.hpp"
 
 #include <hip/hip_runtime.h>
@@ -32,6 +36,7 @@
 #include <deque>
 #include <mutex>
 #include <new>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -58,6 +63,8 @@ struct btlbf_fastx {
 	char* in = nullptr;
 	size_t in_pos = 0, in_len = 0;
 	bool eof = false;
+	bool failed = false;              // a read error: every btlbf_fastx_next from then on returns BTLBF_EIO with `error`
+	std::string path, error;
 	// two output batches: the one handed out by the previous call stays intact during the next parse
 	char* bases[2] = {nullptr, nullptr};
 	uint64_t* starts[2] = {nullptr, nullptr};
@@ -101,9 +108,21 @@ struct btlbf_fastx {
 
 namespace {
 
+// pread that is not defeated by a signal: retried on EINTR, short reads are the caller's business
+ssize_t pread_retry(int fd, void* buf, size_t n, off_t off)
+{
+	for (;;) {
+		const ssize_t r = pread(fd, buf, n, off);
+		if (r >= 0 || errno != EINTR)
+			return r;
+	}
+}
+
+// more input into the window; false at the end of the input and after a read error (r->failed: the input did not end,
+// it could not be read -- an I/O error, or a gzip stream that is cut short or corrupt)
 bool refill(btlbf_fastx* r)
 {
-	if (r->eof)
+	if (r->eof || r->failed)
 		return false;
 	// keep the unread tail (at most a lone '\r' or nothing)
 	const size_t tail = r->in_len - r->in_pos;
@@ -114,12 +133,30 @@ bool refill(btlbf_fastx* r)
 	r->in_len = tail;
 	long got;
 	if (r->fd >= 0) {
-		got = (long)pread(r->fd, r->in + tail, kInBuf - tail, (off_t)r->read_pos);
+		got = (long)pread_retry(r->fd, r->in + tail, kInBuf - tail, (off_t)r->read_pos);
 		if (got > 0)
 			r->read_pos += (uint64_t)got;
+		else if (got < 0) {
+			r->failed = true;
+			r->error = "file \"" + r->path + "\" could not be read: " + strerror(errno);
+		}
 	} else {
 		got = gzread(r->gz, r->in + tail, (unsigned)(kInBuf - tail));
+		if (got <= 0) {
+			// zlib hands out what a truncated stream still holds and then reports 0 bytes: only gzerror tells that from the end
+			int zerr = Z_OK;
+			const char* msg = gzerror(r->gz, &zerr);
+			if (zerr != Z_OK && zerr != Z_STREAM_END) {
+				std::string why = msg && *msg ? msg : "zlib error"; // for Z_ERRNO zlib has kept strerror's text
+				if (why.compare(0, r->path.size() + 2, r->path + ": ") == 0) // zlib puts the path in front
+					why.erase(0, r->path.size() + 2);
+				r->failed = true;
+				r->error = "file \"" + r->path + "\" could not be read: " + why;
+			}
+		}
 	}
+	if (r->failed)
+		return false;
 	if (got <= 0) {
 		r->eof = true;
 		return r->in_len > 0;
@@ -135,16 +172,6 @@ namespace {
 // first record start at or after file offset `begin` (file_size if there is none): FASTA '>' at a line
 // start; 4-line FASTQ: a line starting with '@' whose second successor starts with '+' (a quality line
 // may start with '@', but then the line two below it is a sequence, never a '+'); plain: any line start
-// pread that is not defeated by a signal: retried on EINTR, short reads are the caller's business
-static ssize_t pread_retry(int fd, void* buf, size_t n, off_t off)
-{
-	for (;;) {
-		const ssize_t r = pread(fd, buf, n, off);
-		if (r >= 0 || errno != EINTR)
-			return r;
-	}
-}
-
 // offset of the byte behind the first '\n' at or after `from` (file_size if there is none), reading through a
 // small window that is the caller's and grows only for a line longer than it
 static uint64_t next_line(int fd, uint64_t from, uint64_t file_size, std::vector<char>& w)
@@ -228,6 +255,7 @@ int open_impl(btlbf_fastx** out, const char* path, uint32_t flags, uint32_t k, u
 		}
 		(void)gzbuffer(r->gz, 1u << 20);
 	}
+	r->path = path;
 	r->k = k;
 	r->flags = flags;
 	r->cap_bases = batch_bytes;
@@ -280,12 +308,18 @@ extern "C" void btlbf_fastx_close(btlbf_fastx* r) { delete r; }
 extern "C" uint64_t btlbf_fastx_records(const btlbf_fastx* r) { return r ? r->n_records : 0; }
 
 // Next batch: *bases (n_bases bytes) and *starts (n_seqs + 1 offsets, starts[n_seqs] == n_bases) stay
-// valid until the call after the next one.  n_seqs == 0 at end of input.
+// valid until the call after the next one.  n_seqs == 0 at end of input.  A read error is BTLBF_EIO from the call that
+// meets it (and from every later one): that call delivers nothing, the batches before it stay delivered.
 extern "C" int btlbf_fastx_next(btlbf_fastx* r, const char** bases, uint64_t* n_bases, const uint64_t** starts,
                                 uint64_t* n_seqs)
 {
 	if (!r || !bases || !n_bases || !starts || !n_seqs)
 		return btlbf_set_error(BTLBF_EINVAL, "fastx_next: null argument");
+	*bases = nullptr;
+	*starts = nullptr;
+	*n_bases = *n_seqs = 0;
+	if (r->failed)
+		return btlbf_set_error(BTLBF_EIO, "%s", r->error.c_str());
 	const double t0 = now_s();
 	r->cur ^= 1;
 	char* out = r->bases[r->cur];
@@ -444,6 +478,11 @@ extern "C" int btlbf_fastx_next(btlbf_fastx* r, const char** bases, uint64_t* n_
 				cut(); // the record may go on in the next line
 		}
 	}
+	if (r->failed) {
+		// what this batch holds so far may end in a sequence that the input cuts short: none of it is delivered
+		r->seconds_parse += now_s() - t0;
+		return btlbf_set_error(BTLBF_EIO, "%s", r->error.c_str());
+	}
 	if (r->cont && r->eof && r->in_pos == r->in_len)
 		r->cont = false; // nothing follows
 	st[ns] = nb;
@@ -586,6 +625,10 @@ int run_fastx(btlbf_filter* f, const char* path, uint32_t flags, uint64_t batch_
 	uint64_t dev_cap = std::max<uint64_t>(batch_bytes, std::min<uint64_t>(4ull << 30, std::max<uint64_t>(256ull << 20, btlbf_local_bytes(f) / 32)));
 	if (file_size && !gz)
 		dev_cap = std::max<uint64_t>(batch_bytes, std::min<uint64_t>(dev_cap, file_size + 64));
+	// tests: device batches of a few KiB, so that small files take the slot rotation that real inputs take
+	if (const char* e = getenv("BTLBF_FASTX_DEV_BYTES"))
+		if (const uint64_t v = strtoull(e, nullptr, 10))
+			dev_cap = std::max<uint64_t>(batch_bytes, v);
 	const uint64_t dev_seqs = dev_cap / 16 + 4096;
 
 	std::vector<btlbf_fastx*> readers(T, nullptr);

@@ -641,7 +641,9 @@ typedef struct btlbf_fastx btlbf_fastx;
  * window appears in exactly one batch */
 int btlbf_fastx_open(btlbf_fastx** r, const char* path, uint32_t flags, uint32_t k, uint64_t batch_bytes);
 /* *bases (n_bases bytes) and *starts (n_seqs+1 offsets) stay valid until the call after the next
- * one; n_seqs == 0 at end of input */
+ * one; n_seqs == 0 at end of input.  A read error -- an I/O error, a truncated or corrupt gzip stream -- is
+ * BTLBF_EIO from the call that meets it (the message names the file and the cause): that call delivers no
+ * sequences, the batches delivered before it stay delivered, and btlbf_fastx_records keeps its count */
 int btlbf_fastx_next(btlbf_fastx* r, const char** bases, uint64_t* n_bases, const uint64_t** starts,
                      uint64_t* n_seqs);
 /* one of several readers over the same UNCOMPRESSED file (parallel parsing): delivers the records that

@@ -213,3 +213,91 @@ def test_ranged_readers_tile_the_file(tmp_path):
                     got += rebuild(list(m.fastx_batches(path, k, per_line=lines_mode, batch_bytes=4096,
                                                         byte_range=(a, b), fmt=fmt)), k)
                 assert windows(got, k) == want, (name, lines_mode, cuts)
+
+
+# -------------------------------------------------------------------------------------------------
+# read errors: a damaged .gz is BTLBF_EIO, not the end of the input
+# -------------------------------------------------------------------------------------------------
+def fastq_text(reads, rng):
+    return "".join("@r%d\n%s\n+\n%s\n" % (i, s, "".join(rng.choice("@>+IJ#") for _ in s)) for i, s in enumerate(reads)).encode()
+
+
+def damaged_gz(tmp_path, rng, n_reads=3000):
+    """a gzipped FASTQ of n_reads reads of 60-150 bases -> (reads, intact, cut in half, one byte flipped in the middle)"""
+    reads = [_rand_seq(rng, rng.randrange(60, 151)) for _ in range(n_reads)]
+    data = gzip.compress(fastq_text(reads, rng), mtime=0)
+    paths = [tmp_path / n for n in ("good.fq.gz", "cut.fq.gz", "flipped.fq.gz")]
+    paths[0].write_bytes(data)
+    paths[1].write_bytes(data[:len(data) // 2])
+    paths[2].write_bytes(data[:len(data) // 2] + bytes([data[len(data) // 2] ^ 0xFF]) + data[len(data) // 2 + 1:])
+    return [reads] + paths
+
+
+def delivered_reads(batches, reads, k, batch_bytes, got):
+    """Walks the parser's batches (a generator that may raise) against the reads of the file.  Every sequence must be
+    the next read, whole, or -- where the batch is full and the sequence is its last -- a piece of it, which the next
+    batch continues with the k-1 bases before the cut.  got[0]: reads delivered whole so far."""
+    cur, last_len = None, 0
+    for bases, starts in batches:
+        n = len(starts) - 1
+        for j, (a, b) in enumerate(zip(starts, starts[1:])):
+            piece = bases[a:b].decode()
+            if cur is None:
+                cur = piece
+            else:
+                c = min(k - 1, last_len)
+                assert piece[:c] == cur[len(cur) - c:], (got[0], j)
+                cur += piece[c:]
+            want = reads[got[0]]
+            if cur == want:
+                got[0] += 1
+                cur = None
+            else:  # cut: only at the end of a full batch
+                assert want.startswith(cur) and j == n - 1 and len(bases) == batch_bytes, (got[0], j, cur, want)
+                last_len = len(piece)
+
+
+@pytest.mark.parametrize("whole", [False, True])
+def test_damaged_gzip_is_an_io_error(tmp_path, whole):
+    """a .gz cut in half and one with a byte flipped in the middle: BTLBF_EIO from the parser, with and without
+    BTLBF_FASTX_WHOLE; what the cut file delivers before the error are whole reads of the original, in order"""
+    import btl_bloomfilter_amd as m
+    from btl_bloomfilter_amd._lib import EIO, BtlbfError
+
+    reads, good, cut, flipped = damaged_gz(tmp_path, random.Random(31))
+    assert list(m.fastx_batches(good, K, whole=whole, batch_bytes=4096))  # the intact file parses
+    for path in (cut, flipped):
+        for batch in (0, 4096):
+            got = [0]
+            with pytest.raises(BtlbfError) as e:
+                if whole:
+                    for bases, starts in m.fastx_batches(path, K, whole=True, batch_bytes=batch):
+                        for a, b in zip(starts, starts[1:]):
+                            assert bases[a:b].decode() == reads[got[0]], got[0]
+                            got[0] += 1
+                else:
+                    delivered_reads(m.fastx_batches(path, K, batch_bytes=batch), reads, K, batch, got)
+            assert e.value.code == EIO and path.name in str(e.value), str(e.value)
+            print(path.name, "whole" if whole else "cut", batch, "reads before the error:", got[0], "|", e.value)
+            assert got[0] < len(reads)
+            if batch == 0:
+                assert got[0] == 0  # one batch would have held the file: the failing call delivers none of it
+            elif path is cut:
+                assert got[0] > len(reads) // 4  # the batches before the error stay delivered
+
+
+def test_concatenated_gzip_members_still_parse(tmp_path):
+    """cat a.gz b.gz is a valid gzip file: both members' reads, no error"""
+    import btl_bloomfilter_amd as m
+
+    rng = random.Random(5)
+    ra = [_rand_seq(rng, rng.randrange(60, 151)) for _ in range(200)]
+    rb = [_rand_seq(rng, rng.randrange(60, 151)) for _ in range(150)]
+    p = tmp_path / "ab.fq.gz"
+    p.write_bytes(gzip.compress(fastq_text(ra, rng), mtime=0) + gzip.compress(fastq_text(rb, rng), mtime=0))
+    for batch in (0, 4096):
+        got = [0]
+        delivered_reads(m.fastx_batches(p, K, batch_bytes=batch), ra + rb, K, batch, got)
+        assert got[0] == 350
+    got = rebuild(list(m.fastx_batches(p, K, whole=True, batch_bytes=4096)), K)
+    assert got == ra + rb
