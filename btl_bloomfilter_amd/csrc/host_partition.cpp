@@ -54,16 +54,18 @@ struct PartLevel {
 	uint32_t shift = 0;   // log2(positions per bin)
 	uint32_t wseg = 0;    // level 0 only: bins of `wseg` segments each instead (plan_level0); `shift` is then unused
 	uint32_t alloc_bins = 0; // bins the arrays hold at a time (== bins unless the level is processed in groups)
+	uint32_t packed = 0;  // its chunks hold kPackChunk packed entries, not kChunk words (plan_caps decides)
 	uint64_t cnt_bytes = 0, ent_bytes = 0;
 	uint32_t* cnt = nullptr;
 	uint32_t* ent = nullptr;
-	PartOut out() const { return PartOut{P, regions, cap, cnt, ent}; }
-	PartIn in() const { return PartIn{1, alloc_bins, regions, cap, cnt, ent}; }
+	PartOut out() const { return PartOut{P, regions, cap, packed, cnt, ent}; }
+	PartIn in() const { return PartIn{1, alloc_bins, regions, cap, cnt, ent, packed}; }
 };
 
 struct PartPlan {
 	uint32_t seg_shift = 19;
 	uint64_t n_seg = 0;
+	bool counting = false;   // the array holds counters: every level keeps 32-bit entries (plan_segments)
 	uint32_t group_bins = 0; // level-0 bins split + applied together (one-split plans); 0 = all at once
 	int n_levels = 0; // lv[0] = pass A output (or the exchanged data), lv[1..] = split outputs
 	PartLevel lv[3];
@@ -79,10 +81,11 @@ struct PartPlan {
 
 // chunks a region needs for `mean_entries` expected entries (Poisson: mean + 8 sigma) plus the
 // partially filled chunk flushed at kernel end
-uint32_t chunks_for(double mean_entries, uint32_t tail_chunks)
+// (chunks of `epc` entries: kChunk, or kPackChunk on a packed level)
+uint32_t chunks_for(double mean_entries, uint32_t tail_chunks, uint32_t epc = kChunk)
 {
 	const double m = mean_entries + 8.0 * std::sqrt(mean_entries + 1.0) + 32.0;
-	return (uint32_t)std::min<double>(4.0e9, std::ceil(m / (double)kChunk)) + tail_chunks;
+	return (uint32_t)std::min<double>(4.0e9, std::ceil(m / (double)epc)) + tail_chunks;
 }
 
 unsigned ceil_log2(uint64_t x)
@@ -101,6 +104,7 @@ bool plan_segments(uint64_t mloc, PartPlan& pl, uint32_t unit_shift = 3)
 	// a quarter of the entries take the late path (measured: pass A 63 -> 54 ms at 512 bins; the
 	// read-only pass C loses 0.7 ms per launch with one workgroup per CU)
 	const uint32_t small = 16 + unit_shift;
+	pl.counting = unit_shift == 0;
 	pl.seg_shift = small;
 	if (((mloc + (1ull << small) - 1) >> small) > 512ull * 1024)
 		pl.seg_shift = small + 1;
@@ -181,6 +185,13 @@ bool plan_splits(PartPlan& pl, uint32_t regions_in_total, uint32_t cus = 256)
 	return true;
 }
 
+// tuning knob: BTLBF_PACKED=0 keeps every level on 32-bit entries
+bool packed_enabled()
+{
+	const char* e = getenv("BTLBF_PACKED");
+	return !(e && e[0] == '0');
+}
+
 // capacities + byte sizes for `entries` expected entries in the whole batch
 void plan_caps(PartPlan& pl, double entries, int first_level)
 {
@@ -189,7 +200,12 @@ void plan_caps(PartPlan& pl, double entries, int first_level)
 		PartLevel& l = pl.lv[j];
 		// the last level has n_seg useful bins although bins may be rounded up
 		const double useful = j == pl.n_levels - 1 ? (double)std::min<uint64_t>(pl.n_seg, l.bins) : (double)l.bins;
-		l.cap = chunks_for(entries / (useful * l.regions), 1);
+		// The format of the level, decided here and nowhere else: the LAST split level writes packed chunks -- 48
+		// entries per 128-byte line instead of 32 -- when its rings hold one chunk and its entries fit 20 bits
+		// (part_packs); pass A's output, other split levels and counting filters keep 32-bit entries.
+		// BTLBF_PACKED=0 (tuning knob, read at plan time like BTLBF_SPLIT_BITS) keeps every level on 32-bit entries.
+		l.packed = j >= 1 && j == pl.n_levels - 1 && !pl.counting && part_packs(l.P, l.shift) && packed_enabled();
+		l.cap = chunks_for(entries / (useful * l.regions), 1, part_epc(l.packed));
 		l.alloc_bins = l.bins;
 		if (j >= 1 && pl.group_bins) {
 			l.alloc_bins = pl.group_bins;
@@ -333,7 +349,8 @@ int direct_query_op(const btlbf_filter* f)
 }
 
 // local_probes -- or, with a scratch budget imposed by the caller, what one batch of that budget holds (about 5.5 bytes
-// of scratch per probe): the figure plan_level0's batch-size rule goes by
+// of scratch per probe; 5.3 where the last split level is packed, its arrays holding an eighth of a batch at a time --
+// the rule keeps the larger figure for both): the figure plan_level0's batch-size rule goes by
 double call_probes(const btlbf_filter* f, uint64_t len)
 {
 	const double all = local_probes(f, len);
@@ -1118,7 +1135,7 @@ extern "C" int btlbf_route_seqs(btlbf_filter* f, const char* seq, uint64_t len, 
 	a.counts = counts;
 	a.first_tile = 0;
 	a.n_tiles = part_tiling(f->hp, rp.bins, v.lay, len).n_tiles;
-	PartOut out{rp.bins, rp.regions, rp.cap, static_cast<uint32_t*>(send_cnt), static_cast<uint32_t*>(send_ent)};
+	PartOut out{rp.bins, rp.regions, rp.cap, 0, static_cast<uint32_t*>(send_cnt), static_cast<uint32_t*>(send_ent)};
 	PartSide sd = part_side(f); // (pass A leaves the array alone: whatever misses its rings is spilled)
 	sd.spill_list = spill_list;
 	sd.spill_count = reinterpret_cast<unsigned long long*>(spill_count);

@@ -34,6 +34,16 @@ static constexpr unsigned kBaseGood = 2u;
 // the bytes stored -- half-line writes are not free on this memory system)
 static constexpr uint32_t kChunk = 32;
 static constexpr uint32_t kChunkShift = 5;
+// PACKED chunks: the output of a last split level whose entries need at most kPackBits bits holds them three to a
+// 64-bit word (entry 3w+i of a chunk in bits [20i, 20i+20) of word w, bits 60..63 zero): 48 entries per line instead of
+// 32, six per 16-byte vector.  Only a split whose staging rings hold exactly one chunk writes them (part_packs).
+static constexpr uint32_t kPackChunk = 48;
+static constexpr uint32_t kPackBits = 20;
+static constexpr uint32_t kPackMask = (1u << kPackBits) - 1;
+// can a P-way split to entries of sub_shift bits write packed chunks?  (one-chunk rings: pow2ceil(P) == 1024)
+__host__ __device__ static inline bool part_packs(uint32_t P, uint32_t sub_shift) { return P > 512 && P <= 1024 && sub_shift <= kPackBits; }
+// entries per chunk of a level
+__host__ __device__ static inline uint32_t part_epc(uint32_t packed) { return packed ? kPackChunk : kChunk; }
 
 static constexpr int kMaxHash = 32;  // hash_num supported by the fused kernels
 static constexpr int kMaxSeeds = 16; // spaced seeds per filter
@@ -188,6 +198,7 @@ struct PartOut {
 	uint32_t P;       // bins one workgroup writes (its output block)
 	uint32_t regions; // writers per bin
 	uint32_t cap;     // region capacity in chunks
+	uint32_t packed;  // the chunks hold kPackChunk packed entries each (the last split level, part_packs), not kChunk words
 	uint32_t* cnt;    // [bins * regions] ENTRIES per region
 	uint32_t* ent;    // [bins * regions][cap][32]
 };
@@ -201,6 +212,7 @@ struct PartIn {
 	uint32_t cap;
 	const uint32_t* cnt;
 	const uint32_t* ent;
+	uint32_t packed; // chunks of kPackChunk packed entries (see PartOut); `cap` stays in chunks
 };
 // side channels of a pass
 struct PartSide {

@@ -59,13 +59,94 @@ __device__ __forceinline__ PartLds part_carve(uint8_t* base, uint32_t P)
 	return l;
 }
 
-template <int NT>
+// PK: the rings take PACKED entries (internal.hpp kPackChunk), which are ORed into place -- they start zeroed
+template <int NT, bool PK = false>
 __device__ __forceinline__ void part_init(const PartLds& l, uint32_t P)
 {
 	for (uint32_t b = threadIdx.x; b < P; b += NT) {
 		l.pt[b] = 0;
 		l.fl[b] = 0;
 		l.written[b] = 0;
+	}
+	if (PK) {
+		uint4* st = reinterpret_cast<uint4*>(l.stage);
+		for (uint32_t i = threadIdx.x; i < kStageEntries / 4; i += NT)
+			st[i] = make_uint4(0, 0, 0, 0);
+	}
+}
+
+// ---- packed rings (pass B's last level, part_packs) ----
+// A ring of ONE chunk is empty after every flush, so nothing has to remember where it starts: pt[b] is the bin's entry
+// count alone (ring content + offered this round), and what the returning atomic hands an entry is its slot -- c < 48:
+// slot c, now; 48 <= c < 96: slot c - 48 once the full ring has been flushed (late); beyond: overflow.  Slot s is
+// field s % 3 of the ring's 64-bit word s / 3, and an entry is ORed into it: the lanes that flush a ring zero it
+// behind them (part_round_p2), part_init zeroes all of them.
+__device__ __forceinline__ void part_pack_or(const PartLds& l, uint32_t bin, uint32_t slot, uint32_t v)
+{
+	const uint32_t w = (slot * 43u) >> 7; // slot / 3 for slot < 128
+	const uint32_t f = slot - 3 * w;
+	// one 64-bit LDS OR: two 32-bit ORs on the halves of the word were measured and cost pass B 1.1 ms per launch at C2
+	// (4.98 against 3.89 ms) -- the kernel has no LDS operations to spare
+	unsigned long long* ring = reinterpret_cast<unsigned long long*>(l.stage) + (bin << (kChunkShift - 1));
+	atomicOr(ring + w, (unsigned long long)v << (f * kPackBits));
+}
+// the three entries of a packed word
+__device__ __forceinline__ void part_unpack3(uint32_t lo, uint32_t hi, uint32_t (&e)[3])
+{
+	e[0] = lo & kPackMask;
+	e[1] = ((lo >> kPackBits) | (hi << (32 - kPackBits))) & kPackMask;
+	e[2] = (hi >> (2 * kPackBits - 32)) & kPackMask;
+}
+
+template <int E, int G, bool ALL>
+__device__ __forceinline__ bool part_round_p1_pk(const PartLds& l, const uint32_t (&bin)[E], const uint32_t (&val)[E],
+                                                 const uint32_t live, uint32_t (&old)[E])
+{
+	static_assert(E <= 32 && E % G == 0, "one flag bit per entry; whole groups");
+#pragma unroll
+	for (int g = 0; g < E / G; ++g) {
+		if (ALL || ((live >> g) & 1)) {
+#pragma unroll
+			for (int e = g * G; e < (g + 1) * G; ++e)
+				old[e] = atomicAdd(&l.pt[bin[e]], 1u);
+		} else {
+#pragma unroll
+			for (int e = g * G; e < (g + 1) * G; ++e)
+				old[e] = 0;
+		}
+	}
+	// an entry that finds no room ORs a zero into slot 0 (no branch per entry); phase 3 looks at old[] again
+	bool any_late = false;
+#pragma unroll
+	for (int g = 0; g < E / G; ++g) {
+		if (ALL || ((live >> g) & 1)) {
+#pragma unroll
+			for (int e = g * G; e < (g + 1) * G; ++e) {
+				const bool fits = old[e] < kPackChunk;
+				part_pack_or(l, bin[e], fits ? old[e] : 0u, fits ? val[e] : 0u);
+				any_late |= !fits;
+			}
+		}
+	}
+	return any_late;
+}
+
+template <int E, class OVF>
+__device__ __forceinline__ void part_round_p3_pk(const PartLds& l, const uint32_t (&bin)[E], const uint32_t (&val)[E],
+                                                 const uint32_t (&old)[E], const bool any_late, OVF&& ovf)
+{
+	if (any_late) {
+#pragma unroll
+		for (int e = 0; e < E; ++e) {
+			const uint32_t c = old[e], v = val[e]; // c = 0 for an entry that does not exist
+			if (c >= kPackChunk) {
+				// the full ring was flushed and zeroed in phase 2 (a ring of one chunk always is)
+				if (c < 2 * kPackChunk)
+					part_pack_or(l, bin[e], c - kPackChunk, v);
+				else
+					ovf(bin[e], v);
+			}
+		}
 	}
 }
 
@@ -299,19 +380,34 @@ __device__ __forceinline__ uint32_t part_late_load(const uint32_t* late, uint32_
 // geometry: 0.65 -> 0.49 s per pass).  OWNERS > 0: the first OWNERS waves own all bins (P <= 64 * OWNERS) and only
 // they need to come here (pass A's overlapped schedule: the other waves hash meanwhile); fl[] then holds
 // part_late_word() instead of the flushed count, and each owner wave adds one to *p2_done (LDS) once its words stand.
-template <int NT, int OWNERS = 0, class OVF>
+// PK (packed rings, see part_pack_or): pt[b] is the entry count alone, a ring is flushed when it holds 48 entries and
+// zeroed by the lanes that copy it; the flush list and the line copy are the same.
+template <int NT, int OWNERS = 0, bool PK = false, class OVF>
 __device__ __forceinline__ void part_round_p2(const PartLds& l, const PartOut& o, uint32_t bin0, uint32_t region,
                                               OVF&& ovf, uint32_t* p2_done = nullptr)
 {
 	const uint32_t tid = threadIdx.x;
 	const uint32_t P = o.P;
-	const uint32_t SC = 1u << l.sc_shift, ring = SC - 1;
+	const uint32_t sc_shift = PK ? kChunkShift : l.sc_shift; // (packed rings hold one chunk)
+	const uint32_t SC = 1u << sc_shift, ring = SC - 1;
 	const uint32_t lane = tid & 63;
 	P2_STAMP_DECL;
-	const uint32_t bpw = OWNERS ? (P + OWNERS - 1) / OWNERS : (P >= NT / 2 ? 64u : (P + NT / 64 - 1) / (NT / 64));
+	const uint32_t bpw = PK ? 64u : OWNERS ? (P + OWNERS - 1) / OWNERS : (P >= NT / 2 ? 64u : (P + NT / 64 - 1) / (NT / 64));
 	const uint32_t b = (tid >> 6) * bpw + lane;
 	uint32_t nfl = 0, rd0 = 0, w0 = 0;
-	if (lane < bpw && b < P && (!OWNERS || (tid >> 6) < (uint32_t)OWNERS)) {
+	static_assert(!(PK && OWNERS), "packed rings: pass B only");
+	if (PK) {
+		if (lane < bpw && b < P) {
+			const uint32_t occ = l.pt[b]; // ring content + everything offered this round
+			nfl = occ >= kPackChunk ? 1u : 0u;
+			if (nfl) {
+				const uint32_t tot = occ - kPackChunk; // the late entries, as far as the emptied ring holds them
+				l.pt[b] = tot < kPackChunk ? tot : kPackChunk;
+				w0 = l.written[b];
+				l.written[b] = w0 + 1;
+			}
+		}
+	} else if (lane < bpw && b < P && (!OWNERS || (tid >> 6) < (uint32_t)OWNERS)) {
 		const uint32_t w = l.pt[b];
 		const uint32_t occ = w & 0xffffu;           // ring content + everything offered this round
 		const uint32_t avail = occ < SC ? occ : SC; // entries that really sit in the ring
@@ -346,10 +442,10 @@ __device__ __forceinline__ void part_round_p2(const PartLds& l, const PartOut& o
 	// in the wave's slice (64 bins * SC/kChunk items)
 	const uint32_t incl = wave_scan_incl(nfl);
 	const uint32_t total = __builtin_amdgcn_readlane(incl, 63);
-	const uint32_t slice = (tid >> 6) * ((bpw << l.sc_shift) >> kChunkShift);
+	const uint32_t slice = (tid >> 6) * ((bpw << sc_shift) >> kChunkShift);
 	// a flush item is (chunk of the staging area, chunk of the output array): both are worked out here, once
 	// per chunk, and the part that depends on the bin alone is the same in every round (hoisted)
-	const uint32_t cshift = l.sc_shift - kChunkShift; // log2(chunks per ring)
+	const uint32_t cshift = sc_shift - kChunkShift; // log2(chunks per ring)
 	const uint32_t cbase = ((bin0 + b) * o.regions + region) * o.cap;
 	for (uint32_t c = 0; c < nfl; ++c) {
 		const uint32_t j = slice + incl - nfl + c;
@@ -366,6 +462,8 @@ __device__ __forceinline__ void part_round_p2(const PartLds& l, const PartOut& o
 	for (uint32_t j = lane / kLanesPerChunk; j < total; j += 64 / kLanesPerChunk) {
 		const uint32_t it = l.flist[slice + j], wc = l.fwc[slice + j];
 		const uint4 v = *reinterpret_cast<const uint4*>(&l.stage[it * kChunk + l4 * 4]);
+		if (PK)
+			*reinterpret_cast<uint4*>(&l.stage[it * kChunk + l4 * 4]) = make_uint4(0, 0, 0, 0);
 		if (wc != 0xffffffffu) {
 #ifdef BTLBF_NT_FLUSH // pass A (part_hash_inst.hip defines it): streaming stores for the chunks, so that they do not
 			// push the late image and the reads out of the L2 -- pass A 39.35 -> 39.0 ms, query 41.3 -> 40.8; pass B, whose
@@ -376,6 +474,16 @@ __device__ __forceinline__ void part_round_p2(const PartLds& l, const PartOut& o
 #else
 			*reinterpret_cast<uint4*>(&o.ent[(uint64_t)wc * kChunk + l4 * 4]) = v;
 #endif
+		} else if (PK) { // a flushed ring is full: all six entries of the vector are real
+			uint32_t e3[3];
+			part_unpack3(v.x, v.y, e3);
+			ovf(it, e3[0]);
+			ovf(it, e3[1]);
+			ovf(it, e3[2]);
+			part_unpack3(v.z, v.w, e3);
+			ovf(it, e3[0]);
+			ovf(it, e3[1]);
+			ovf(it, e3[2]);
 		} else {
 			const uint32_t fb = it >> cshift;
 			ovf(fb, v.x);
@@ -410,19 +518,22 @@ __device__ __forceinline__ void part_round_p3(const PartLds& l, const uint32_t (
 	}
 }
 
-template <int NT, int E, int G, bool ALL = false, class OVF>
+template <int NT, int E, int G, bool ALL = false, bool PK = false, class OVF>
 __device__ __forceinline__ void part_round(const PartLds& l, const PartOut& o, uint32_t bin0, uint32_t region,
                                            const uint32_t (&bin)[E], const uint32_t (&val)[E], const uint32_t live,
                                            OVF&& ovf STAMP_ARGS)
 {
 	uint32_t old[E];
-	const bool any_late = part_round_p1<E, G, ALL>(l, bin, val, live, old);
+	const bool any_late = PK ? part_round_p1_pk<E, G, ALL>(l, bin, val, live, old) : part_round_p1<E, G, ALL>(l, bin, val, live, old);
 	__syncthreads();
 	STAMP(4);
-	part_round_p2<NT>(l, o, bin0, region, ovf);
+	part_round_p2<NT, 0, PK>(l, o, bin0, region, ovf);
 	__syncthreads();
 	STAMP(6);
-	part_round_p3<E>(l, bin, val, old, any_late, ovf);
+	if (PK)
+		part_round_p3_pk<E>(l, bin, val, old, any_late, ovf);
+	else
+		part_round_p3<E>(l, bin, val, old, any_late, ovf);
 	STAMP(7);
 }
 
@@ -456,6 +567,45 @@ __device__ __forceinline__ void part_finish(const PartLds& l, const PartOut& o, 
 		}
 		if (ln == 0)
 			o.cnt[(bin0 + b) * o.regions + region] = full * kChunk + stored;
+	}
+}
+
+// The same for packed rings: a bin has at most one (partial or full) chunk staged.  The fields behind the region's last
+// entry, up to the end of its last 16-byte vector, repeat that entry: readers of a bit filter take whole vectors.
+template <int NT, class OVF>
+__device__ __forceinline__ void part_finish_pk(const PartLds& l, const PartOut& o, uint32_t bin0, uint32_t region,
+                                               OVF&& ovf)
+{
+	__syncthreads();
+	const uint32_t tid = threadIdx.x, ln = tid & (kChunk - 1);
+	for (uint32_t b = tid / kChunk; b < o.P; b += NT / kChunk) {
+		const uint32_t n = l.pt[b]; // <= kPackChunk
+		const uint32_t w0 = l.written[b];
+		const uint32_t full = w0 < o.cap ? w0 : o.cap; // chunks of this region that really hold data
+		const uint64_t o0 = (uint64_t)((bin0 + b) * o.regions + region) * o.cap;
+		if (n && ln < kChunk / 2) { // one lane per 64-bit word
+			const unsigned long long* ring = reinterpret_cast<const unsigned long long*>(l.stage) + (b << (kChunkShift - 1));
+			const unsigned long long word = ring[ln];
+			const uint32_t lw = ((n - 1) * 43u) >> 7, lf = (n - 1) - 3 * lw;
+			const uint32_t last = (uint32_t)(ring[lw] >> (lf * kPackBits)) & kPackMask;
+			const uint32_t n_pad = (n + 5) / 6 * 6;
+			uint32_t e3[3];
+			part_unpack3((uint32_t)word, (uint32_t)(word >> 32), e3);
+			unsigned long long outw = 0;
+#pragma unroll
+			for (uint32_t f = 0; f < 3; ++f) {
+				const uint32_t i = 3 * ln + f;
+				const uint32_t e = i < n ? e3[f] : last;
+				if (i < n_pad)
+					outw |= (unsigned long long)e << (f * kPackBits);
+				if (w0 >= o.cap && i < n)
+					ovf(b, e);
+			}
+			if (w0 < o.cap)
+				reinterpret_cast<unsigned long long*>(o.ent)[(o0 + w0) * (kChunk / 2) + ln] = outw;
+		}
+		if (ln == 0)
+			o.cnt[(bin0 + b) * o.regions + region] = full * kPackChunk + (w0 < o.cap ? n : 0u);
 	}
 }
 

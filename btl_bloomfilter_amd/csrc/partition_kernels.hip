@@ -23,6 +23,9 @@
 // not fit (a region over capacity, or a bin that receives more than its ring and the space freed by
 // one flush hold inside one round) take the overflow path: applied to the filter directly (single
 // GPU) or appended to a spill list of global positions (multi-GPU routing) -- never dropped.
+// The LAST split level of a bit filter writes PACKED chunks where it can (internal.hpp kPackChunk, part_packs: a 513- to
+// 1024-way split to entries of at most 20 bits): three entries per 64-bit word, 48 per line; its rings hold the packed
+// words themselves (partition_core.hpp part_pack_or), and pass C takes a 16-byte vector as six entries.
 #include "partition_core.hpp"
 #include <algorithm>
 
@@ -59,7 +62,8 @@ __device__ __forceinline__ uint32_t part_in_region(const PartIn& in, uint32_t b,
 // scratch of the split levels small.  Input bin i is bin i + abs_off of its level in absolute terms
 // (the input arrays themselves are group-relative from the second split level on).
 // EXACT: every entry counts (counter increments): the padded tail of a region is not taken whole.
-template <bool QUERY, bool EXACT>
+// PK: the output is written as packed chunks (out.packed: internal.hpp part_packs); the input never is.
+template <bool QUERY, bool EXACT, bool PK>
 __global__ __launch_bounds__(kPartThreads) void part_split_kernel(void* filter, const PartIn in, const PartOut out,
                                                                  const uint32_t slices, const uint32_t sub_shift,
                                                                  const uint32_t in_shift, const uint32_t first_in,
@@ -69,7 +73,8 @@ __global__ __launch_bounds__(kPartThreads) void part_split_kernel(void* filter, 
 	const uint32_t tid = threadIdx.x;
 	const uint32_t b = first_in + blockIdx.x / slices, g = blockIdx.x % slices;
 	const PartLds pl = part_carve(dyn, out.P);
-	part_init<kPartThreads>(pl, out.P);
+	static_assert(!(PK && EXACT), "counting filters keep 32-bit entries");
+	part_init<kPartThreads, PK>(pl, out.P);
 	uint32_t* words = static_cast<uint32_t*>(filter);
 	const uint32_t sub_mask = (1u << sub_shift) - 1;
 	const uint64_t bin_base = part_bin_base(sd, b + abs_off, in_shift);
@@ -84,7 +89,7 @@ __global__ __launch_bounds__(kPartThreads) void part_split_kernel(void* filter, 
 	for (uint32_t r = g; r < n_regions_in; r += slices) {
 		const uint32_t reg = part_in_region(in, b, r);
 		uint32_t n = in.cnt[reg];
-		if (n > in.cap * kChunk)
+		if (n > in.cap * kChunk) // (a split's input is never packed: launch_part_split)
 			n = in.cap * kChunk;
 		const uint4* src = reinterpret_cast<const uint4*>(in.ent + (uint64_t)reg * in.cap * kChunk);
 		const uint32_t n_vec = (n + 3) / 4;
@@ -115,7 +120,7 @@ __global__ __launch_bounds__(kPartThreads) void part_split_kernel(void* filter, 
 			// EXACT: every entry counts, so the padded tail of the last vector is not taken whole
 			const bool full = EXACT ? (uint64_t)(base + kPartThreads * kVec) * 4 <= n : base + kPartThreads * kVec <= n_vec;
 			if (full) {
-				part_round<kPartThreads, kVec * 4, EXACT ? 1 : 4, true>(pl, out, bin0, g, bin, val, 0, ovf STAMP_PASS);
+				part_round<kPartThreads, kVec * 4, EXACT ? 1 : 4, true, PK>(pl, out, bin0, g, bin, val, 0, ovf STAMP_PASS);
 			} else {
 				uint32_t live = 0;
 #pragma unroll
@@ -128,7 +133,7 @@ __global__ __launch_bounds__(kPartThreads) void part_split_kernel(void* filter, 
 						if (EXACT)
 							live |= (uint32_t)(vi * 4 + c < n) << (v * 4 + c);
 				}
-				part_round<kPartThreads, kVec * 4, EXACT ? 1 : 4, false>(pl, out, bin0, g, bin, val, live, ovf STAMP_PASS);
+				part_round<kPartThreads, kVec * 4, EXACT ? 1 : 4, false, PK>(pl, out, bin0, g, bin, val, live, ovf STAMP_PASS);
 			}
 		};
 		// two register sets take turns (no copies between rounds)
@@ -146,7 +151,10 @@ __global__ __launch_bounds__(kPartThreads) void part_split_kernel(void* filter, 
 			round(vb, base1);
 		}
 	}
-	part_finish<kPartThreads>(pl, out, bin0, g, ovf);
+	if (PK)
+		part_finish_pk<kPartThreads>(pl, out, bin0, g, ovf);
+	else
+		part_finish<kPartThreads>(pl, out, bin0, g, ovf);
 }
 
 // ---- pass C --------------------------------------------------------------------------------------
@@ -191,12 +199,51 @@ __device__ __forceinline__ void apply_entry(uint32_t* lds, uint32_t e, const Par
 	}
 }
 
+// one 16-byte vector of a region with `left` entries from its first one on: four entries, or six packed ones (PK).
+// Bit filters take it whole: a region's last vector is padded with copies of its last entry (part_finish), and a
+// repeated position changes nothing for OR / test; the counting passes take exactly the entries there are.
+template <int MODE, bool PK>
+__device__ __forceinline__ void apply_vec(uint32_t* lds, const uint4& q, uint32_t left, const PartSide& sd, uint64_t seg_base)
+{
+	if (PK) {
+		static_assert(!PK || MODE < APPLY_CNT_INC, "counting filters keep 32-bit entries");
+		if (left > 0) {
+			uint32_t a[3], b[3];
+			part_unpack3(q.x, q.y, a);
+			part_unpack3(q.z, q.w, b);
+			apply_entry<MODE>(lds, a[0], sd, seg_base);
+			apply_entry<MODE>(lds, a[1], sd, seg_base);
+			apply_entry<MODE>(lds, a[2], sd, seg_base);
+			apply_entry<MODE>(lds, b[0], sd, seg_base);
+			apply_entry<MODE>(lds, b[1], sd, seg_base);
+			apply_entry<MODE>(lds, b[2], sd, seg_base);
+		}
+	} else if (MODE < APPLY_CNT_INC) {
+		if (left > 0) {
+			apply_entry<MODE>(lds, q.x, sd, seg_base);
+			apply_entry<MODE>(lds, q.y, sd, seg_base);
+			apply_entry<MODE>(lds, q.z, sd, seg_base);
+			apply_entry<MODE>(lds, q.w, sd, seg_base);
+		}
+	} else {
+		if (left > 0)
+			apply_entry<MODE>(lds, q.x, sd, seg_base);
+		if (left > 1)
+			apply_entry<MODE>(lds, q.y, sd, seg_base);
+		if (left > 2)
+			apply_entry<MODE>(lds, q.z, sd, seg_base);
+		if (left > 3)
+			apply_entry<MODE>(lds, q.w, sd, seg_base);
+	}
+}
+
 // Memory-level parallelism is what this kernel lives on: the segment is fetched with 8 independent
 // 16-byte loads per thread, and the entries of ALL regions are walked as one virtual array with 4
 // independent loads per thread in flight (the first batch is requested before the segment is waited for).
 // NT = 512 for 64 KiB segments (two workgroups per CU), 1024 for 128 KiB segments (one per CU).
 // Every region is read up to its exact entry count (its last vector may be padded).
-template <int MODE, int NT>
+// PK: the input holds packed chunks (in.packed): kPackChunk entries per chunk, six per vector.
+template <int MODE, int NT, bool PK>
 __global__ __launch_bounds__(NT) void part_apply_kernel(uint8_t* filter, uint64_t local_bytes,
                                                         uint32_t seg_shift, uint32_t seg_first,
                                                         const PartIn in, const PartSide sd)
@@ -212,7 +259,9 @@ __global__ __launch_bounds__(NT) void part_apply_kernel(uint8_t* filter, uint64_
 	const uint32_t ibin = blockIdx.x;
 	const uint32_t seg = seg_first + blockIdx.x;
 	const uint32_t n_regions = in.blocks * in.regions_per_block;
-	const uint32_t cap_entries = in.cap * kChunk;
+	constexpr uint32_t kVecE = PK ? 6 : 4;                // entries per 16-byte vector
+	const uint32_t cap_entries = in.cap * (PK ? kPackChunk : kChunk);
+	const uint32_t cap_words = in.cap * kChunk;           // a region in uint32 words, whatever it holds
 	const bool tabled = n_regions <= kApplyMaxRegions;
 	if (tid == 0)
 		any = 0;
@@ -250,7 +299,7 @@ __global__ __launch_bounds__(NT) void part_apply_kernel(uint8_t* filter, uint64_
 	uint4 q[kEntU];
 #define BTLBF_SETTLE(r, i)                               \
 	while ((r) < n_regions) {                            \
-		const uint32_t nev__ = (r_n[(r)] + 3) / 4;       \
+		const uint32_t nev__ = (r_n[(r)] + kVecE - 1) / kVecE; \
 		if ((i) < nev__)                                 \
 			break;                                       \
 		(i) -= nev__;                                    \
@@ -261,8 +310,8 @@ __global__ __launch_bounds__(NT) void part_apply_kernel(uint8_t* filter, uint64_
 		lft = 0;                                                                                               \
 		dst = make_uint4(0, 0, 0, 0);                                                                          \
 		if (wr[u] < n_regions) {                                                                               \
-			lft = r_n[wr[u]] - wi[u] * 4;                                                                      \
-			dst = reinterpret_cast<const uint4*>(in.ent + (uint64_t)r_reg[wr[u]] * cap_entries)[wi[u]];        \
+			lft = r_n[wr[u]] - wi[u] * kVecE;                                                                  \
+			dst = reinterpret_cast<const uint4*>(in.ent + (uint64_t)r_reg[wr[u]] * cap_words)[wi[u]];          \
 		}                                                                                                      \
 	} while (0)
 	// FEW regions (the usual case behind a split pass: one region per slice): they are walked one after the
@@ -278,7 +327,7 @@ __global__ __launch_bounds__(NT) void part_apply_kernel(uint8_t* filter, uint64_
 	// region sizes are.
 	uint32_t f_r = 0, f_off = 0;
 	auto few_nvec = [&](uint32_t r) -> uint32_t {
-		return ((uint32_t)__builtin_amdgcn_readfirstlane((int)r_n[r]) + 3) / 4;
+		return ((uint32_t)__builtin_amdgcn_readfirstlane((int)r_n[r]) + kVecE - 1) / kVecE;
 	};
 	auto few_skip = [&]() { // -> a region with vectors left, or f_r == n_regions
 		while (f_r < n_regions && f_off >= few_nvec(f_r)) {
@@ -287,13 +336,13 @@ __global__ __launch_bounds__(NT) void part_apply_kernel(uint8_t* filter, uint64_
 		}
 	};
 	auto few_request = [&](uint4 (&d)[kFewU], uint32_t (&lf)[kFewU]) {
-		const uint32_t n0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)r_n[f_r]), nv0 = (n0 + 3) / 4;
+		const uint32_t n0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)r_n[f_r]), nv0 = (n0 + kVecE - 1) / kVecE;
 		const uint32_t reg0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)r_reg[f_r]);
 		const bool two = f_r + 1 < n_regions;
-		const uint32_t n1 = two ? (uint32_t)__builtin_amdgcn_readfirstlane((int)r_n[two ? f_r + 1 : f_r]) : 0u, nv1 = (n1 + 3) / 4;
+		const uint32_t n1 = two ? (uint32_t)__builtin_amdgcn_readfirstlane((int)r_n[two ? f_r + 1 : f_r]) : 0u, nv1 = (n1 + kVecE - 1) / kVecE;
 		const uint32_t reg1 = two ? (uint32_t)__builtin_amdgcn_readfirstlane((int)r_reg[two ? f_r + 1 : f_r]) : reg0;
-		const uint4* src0 = reinterpret_cast<const uint4*>(in.ent + (uint64_t)reg0 * cap_entries);
-		const uint4* src1 = reinterpret_cast<const uint4*>(in.ent + (uint64_t)reg1 * cap_entries);
+		const uint4* src0 = reinterpret_cast<const uint4*>(in.ent + (uint64_t)reg0 * cap_words);
+		const uint4* src1 = reinterpret_cast<const uint4*>(in.ent + (uint64_t)reg1 * cap_words);
 #pragma unroll
 		for (int u = 0; u < kFewU; ++u) {
 			const uint32_t v = f_off + (uint32_t)u * NT + tid; // vector index counted from the start of region f_r
@@ -301,10 +350,10 @@ __global__ __launch_bounds__(NT) void part_apply_kernel(uint8_t* filter, uint64_
 			d[u] = make_uint4(0, 0, 0, 0);
 			if (v < nv0) {
 				d[u] = kNtEnt ? nt_load4(src0 + v) : src0[v];
-				lf[u] = n0 - v * 4;
+				lf[u] = n0 - v * kVecE;
 			} else if (v - nv0 < nv1) {
 				d[u] = kNtEnt ? nt_load4(src1 + (v - nv0)) : src1[v - nv0];
-				lf[u] = n1 - (v - nv0) * 4;
+				lf[u] = n1 - (v - nv0) * kVecE;
 			}
 		}
 		const uint32_t end = f_off + (uint32_t)(kFewU * NT);
@@ -362,23 +411,7 @@ __global__ __launch_bounds__(NT) void part_apply_kernel(uint8_t* filter, uint64_
 				few_request(nq, nl);
 #pragma unroll
 			for (int u = 0; u < kFewU; ++u) {
-				if (MODE < APPLY_CNT_INC) {
-					if (fl[u] > 0) { // whole vectors: see below
-						apply_entry<MODE>(lds, fq[u].x, sd, seg_base);
-						apply_entry<MODE>(lds, fq[u].y, sd, seg_base);
-						apply_entry<MODE>(lds, fq[u].z, sd, seg_base);
-						apply_entry<MODE>(lds, fq[u].w, sd, seg_base);
-					}
-				} else {
-					if (fl[u] > 0)
-						apply_entry<MODE>(lds, fq[u].x, sd, seg_base);
-					if (fl[u] > 1)
-						apply_entry<MODE>(lds, fq[u].y, sd, seg_base);
-					if (fl[u] > 2)
-						apply_entry<MODE>(lds, fq[u].z, sd, seg_base);
-					if (fl[u] > 3)
-						apply_entry<MODE>(lds, fq[u].w, sd, seg_base);
-				}
+				apply_vec<MODE, PK>(lds, fq[u], fl[u], sd, seg_base);
 				if (more) {
 					fq[u] = nq[u];
 					fl[u] = nl[u];
@@ -398,25 +431,7 @@ __global__ __launch_bounds__(NT) void part_apply_kernel(uint8_t* filter, uint64_
 			}
 #pragma unroll
 			for (int u = 0; u < kEntU; ++u) {
-				if (MODE < APPLY_CNT_INC) {
-					// bit filter: a region's last vector is padded with copies of its last entry (part_finish),
-					// and a repeated position changes nothing for OR / test -- whole vectors, one test
-					if (left[u] > 0) {
-						apply_entry<MODE>(lds, q[u].x, sd, seg_base);
-						apply_entry<MODE>(lds, q[u].y, sd, seg_base);
-						apply_entry<MODE>(lds, q[u].z, sd, seg_base);
-						apply_entry<MODE>(lds, q[u].w, sd, seg_base);
-					}
-				} else {
-					if (left[u] > 0)
-						apply_entry<MODE>(lds, q[u].x, sd, seg_base);
-					if (left[u] > 1)
-						apply_entry<MODE>(lds, q[u].y, sd, seg_base);
-					if (left[u] > 2)
-						apply_entry<MODE>(lds, q[u].z, sd, seg_base);
-					if (left[u] > 3)
-						apply_entry<MODE>(lds, q[u].w, sd, seg_base);
-				}
+				apply_vec<MODE, PK>(lds, q[u], left[u], sd, seg_base);
 				q[u] = nq[u];
 				left[u] = nleft[u];
 			}
@@ -429,7 +444,17 @@ __global__ __launch_bounds__(NT) void part_apply_kernel(uint8_t* filter, uint64_
 			uint32_t n = in.cnt[reg];
 			if (n > cap_entries)
 				n = cap_entries;
-			const uint32_t* e1 = in.ent + (uint64_t)reg * cap_entries;
+			const uint32_t* e1 = in.ent + (uint64_t)reg * cap_words;
+			if (PK) { // word by word: the fields behind the last entry repeat it (bit filters only)
+				for (uint32_t i = tid; i < (n + 2) / 3; i += NT) {
+					uint32_t e3[3];
+					part_unpack3(e1[2 * i], e1[2 * i + 1], e3);
+					apply_entry<MODE>(lds, e3[0], sd, seg_base);
+					apply_entry<MODE>(lds, e3[1], sd, seg_base);
+					apply_entry<MODE>(lds, e3[2], sd, seg_base);
+				}
+				continue;
+			}
 			for (uint32_t i = tid; i < n; i += NT)
 				apply_entry<MODE>(lds, e1[i], sd, seg_base);
 		}
@@ -611,26 +636,33 @@ hipError_t launch_part_split(void* filter, const PartIn& in, uint32_t first_in, 
 {
 	if (n_in_bins == 0)
 		return hipSuccess;
+	// packed output: one-chunk rings, entries of at most kPackBits bits, no counting passes; packed input: never
+	if (in.packed || (out.packed && (!part_packs(out.P, sub_shift) || exact || sd.counting)))
+		return hipErrorInvalidValue;
 	const size_t dyn = part_lds_bytes(out.P);
 	const uint32_t slices = out.regions;
 	const dim3 grid(n_in_bins * slices);
-#define BTLBF_SLAUNCH(Q, E)                                                                                    \
+#define BTLBF_SLAUNCH(Q, E, PK)                                                                                \
 	do {                                                                                                       \
-		hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&part_split_kernel<Q, E>),            \
+		hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&part_split_kernel<Q, E, PK>),        \
 		                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);              \
 		if (e != hipSuccess)                                                                                   \
 			return e;                                                                                          \
-		hipLaunchKernelGGL((part_split_kernel<Q, E>), grid, dim3(kPartThreads), dyn, s, filter, in, out, slices, \
+		hipLaunchKernelGGL((part_split_kernel<Q, E, PK>), grid, dim3(kPartThreads), dyn, s, filter, in, out, slices, \
 		                   sub_shift, in_shift, first_in, abs_first - first_in, sd);                            \
 	} while (0)
-	if (query && exact)
-		BTLBF_SLAUNCH(true, true);
+	if (out.packed && query)
+		BTLBF_SLAUNCH(true, false, true);
+	else if (out.packed)
+		BTLBF_SLAUNCH(false, false, true);
+	else if (query && exact)
+		BTLBF_SLAUNCH(true, true, false);
 	else if (query)
-		BTLBF_SLAUNCH(true, false);
+		BTLBF_SLAUNCH(true, false, false);
 	else if (exact)
-		BTLBF_SLAUNCH(false, true);
+		BTLBF_SLAUNCH(false, true, false);
 	else
-		BTLBF_SLAUNCH(false, false);
+		BTLBF_SLAUNCH(false, false, false);
 #undef BTLBF_SLAUNCH
 	return hipGetLastError();
 }
@@ -640,33 +672,41 @@ hipError_t launch_part_apply(void* filter, uint64_t local_bytes, uint32_t seg_sh
 {
 	if (n_seg == 0)
 		return hipSuccess;
+	if (in.packed && (sd.counting || seg_shift > kPackBits))
+		return hipErrorInvalidValue;
 	const int mode = (sd.counting ? APPLY_CNT_INC : APPLY_BIT_OR) + (query ? 1 : 0);
 	const size_t dyn = (size_t)1 << (seg_shift - (sd.counting ? 0 : 3)); // bytes of one segment
-#define BTLBF_ALAUNCH(M, NT)                                                                                   \
+#define BTLBF_ALAUNCH(M, NT, PK)                                                                                 \
 	do {                                                                                                       \
-		hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&part_apply_kernel<M, NT>),           \
+		hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&part_apply_kernel<M, NT, PK>),       \
 		                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);              \
 		if (e != hipSuccess)                                                                                   \
 			return e;                                                                                          \
-		hipLaunchKernelGGL((part_apply_kernel<M, NT>), dim3((unsigned)n_seg), dim3(NT), dyn, s,                \
+		hipLaunchKernelGGL((part_apply_kernel<M, NT, PK>), dim3((unsigned)n_seg), dim3(NT), dyn, s,            \
 		                   static_cast<uint8_t*>(filter), local_bytes, seg_shift, (uint32_t)seg_first, in, sd); \
 	} while (0)
-#define BTLBF_ALAUNCH_M(NT)                      \
-	do {                                         \
-		switch (mode) {                          \
-		case APPLY_BIT_OR:                       \
-			BTLBF_ALAUNCH(APPLY_BIT_OR, NT);     \
-			break;                               \
-		case APPLY_BIT_TEST:                     \
-			BTLBF_ALAUNCH(APPLY_BIT_TEST, NT);   \
-			break;                               \
-		case APPLY_CNT_INC:                      \
-			BTLBF_ALAUNCH(APPLY_CNT_INC, NT);    \
-			break;                               \
-		default:                                 \
-			BTLBF_ALAUNCH(APPLY_CNT_TEST, NT);   \
-			break;                               \
-		}                                        \
+#define BTLBF_ALAUNCH_M(NT)                                 \
+	do {                                                    \
+		switch (mode) {                                     \
+		case APPLY_BIT_OR:                                  \
+			if (in.packed)                                  \
+				BTLBF_ALAUNCH(APPLY_BIT_OR, NT, true);      \
+			else                                            \
+				BTLBF_ALAUNCH(APPLY_BIT_OR, NT, false);     \
+			break;                                          \
+		case APPLY_BIT_TEST:                                \
+			if (in.packed)                                  \
+				BTLBF_ALAUNCH(APPLY_BIT_TEST, NT, true);    \
+			else                                            \
+				BTLBF_ALAUNCH(APPLY_BIT_TEST, NT, false);   \
+			break;                                          \
+		case APPLY_CNT_INC:                                 \
+			BTLBF_ALAUNCH(APPLY_CNT_INC, NT, false);        \
+			break;                                          \
+		default:                                            \
+			BTLBF_ALAUNCH(APPLY_CNT_TEST, NT, false);       \
+			break;                                          \
+		}                                                   \
 	} while (0)
 	if (dyn > 64 * 1024) // 128 KiB segments: one workgroup per CU
 		BTLBF_ALAUNCH_M(1024);
