@@ -677,6 +677,26 @@ __global__ __launch_bounds__(kPartThreads, 1) void part_hash_ov_kernel(const Seq
 	}
 }
 
+// The overlapped schedule exists for at most four hashes per k-mer (see launch_hash_h for the measurements) ...
+template <int H>
+static constexpr bool kOvH = H <= 4;
+// ... and not for spaced seeds: those kernels are not even instantiated.  The instantiation a launch takes:
+using PassAKernel = void (*)(SeqArgs, PartOut, uint32_t, PartSide);
+template <int H, bool Q, bool P, bool S, bool W>
+static PassAKernel pass_a_kernel(bool overlapped, bool aux)
+{
+	if constexpr (!S && kOvH<H>) {
+		if (overlapped)
+			return aux ? &part_hash_ov_kernel<H, P, S, Q, W, true> : &part_hash_ov_kernel<H, P, S, Q, W, false>;
+	}
+	return &part_hash_kernel<H, P, S, Q, W>;
+}
+template <int H, bool Q, bool P, bool S>
+static PassAKernel pass_a_kernel(bool window, bool overlapped, bool aux)
+{
+	return window ? pass_a_kernel<H, Q, P, S, true>(overlapped, aux) : pass_a_kernel<H, Q, P, S, false>(overlapped, aux);
+}
+
 template <int H, bool Q>
 static hipError_t launch_hash_h(const SeqArgs& a, const PartOut& out, uint32_t bin_shift, const PartSide& sd,
                                 size_t dyn, hipStream_t s)
@@ -693,59 +713,21 @@ static hipError_t launch_hash_h(const SeqArgs& a, const PartOut& out, uint32_t b
 	// a round's 4h entries per lane no longer fit the registers beside the hash state -- h = 5: 34.0 / 41.6 ms insert /
 	// query per 3.6x10^9 k-mers against 34.3 / 35.1 with the plain kernel, h = 6: 52.2 / 62.2 against 41.7 / 42.6,
 	// h = 8: 230 / 257 against 97 / 169; h = 3: 19.5 / 20.3 against 21.3 / 21.8)
-	constexpr bool kOvH = H <= 4;
 	// (spaced seeds keep the plain schedule: the overlapped kernel runs them, bit-identically, but 9 % slower -- 99.7
 	// against 91.3 ms per 6x10^9 k-mers at BASELINE config 5 -- its registers are full without the seeds' running values)
 	const bool aux = a.sb_words != 0 || (a.read_mask != nullptr && a.rg_reads != 0); // (see part_hash_ov_kernel)
-	const bool overlapped = kOvH && !spaced && out.P <= 64u * kOvOwners && !ov_off && sd.late_buf != nullptr &&
+	const bool overlapped = kOvH<H> && !spaced && out.P <= 64u * kOvOwners && !ov_off && sd.late_buf != nullptr &&
 	                        sd.late_cap >= kStageEntries;
-#define BTLBF_PLAUNCH(P, S, W)                                                                                      \
-	do {                                                                                                            \
-		if constexpr (!S && kOvH) {                                                                                 \
-			if (overlapped && aux) {                                                                                \
-				hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&part_hash_ov_kernel<H, P, S, Q, W, true>), \
-				                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);            \
-				if (e != hipSuccess)                                                                                \
-					return e;                                                                                       \
-				hipLaunchKernelGGL((part_hash_ov_kernel<H, P, S, Q, W, true>), dim3(out.regions), dim3(kPartThreads), dyn, s, \
-				                   a, out, bin_shift, sd);                                                          \
-				break;                                                                                              \
-			}                                                                                                       \
-			if (overlapped) {                                                                                       \
-				hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&part_hash_ov_kernel<H, P, S, Q, W, false>), \
-				                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);            \
-				if (e != hipSuccess)                                                                                \
-					return e;                                                                                       \
-				hipLaunchKernelGGL((part_hash_ov_kernel<H, P, S, Q, W, false>), dim3(out.regions), dim3(kPartThreads), dyn, s, \
-				                   a, out, bin_shift, sd);                                                          \
-				break;                                                                                              \
-			}                                                                                                       \
-		}                                                                                                           \
-		hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&part_hash_kernel<H, P, S, Q, W>),           \
-		                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);                    \
-		if (e != hipSuccess)                                                                                        \
-			return e;                                                                                               \
-		hipLaunchKernelGGL((part_hash_kernel<H, P, S, Q, W>), dim3(out.regions), dim3(kPartThreads), dyn, s, a, out,  \
-		                   bin_shift, sd);                                                                          \
-	} while (0)
-#define BTLBF_PLAUNCH_W(P, S)        \
-	do {                             \
-		if (window)                  \
-			BTLBF_PLAUNCH(P, S, true);  \
-		else                         \
-			BTLBF_PLAUNCH(P, S, false); \
-	} while (0)
+	PassAKernel kernel; // (the order of these four is the order of the kernels in the code object)
 	if (pow2 && !spaced)
-		BTLBF_PLAUNCH_W(true, false);
+		kernel = pass_a_kernel<H, Q, true, false>(window, overlapped, aux);
 	else if (!pow2 && !spaced)
-		BTLBF_PLAUNCH_W(false, false);
+		kernel = pass_a_kernel<H, Q, false, false>(window, overlapped, aux);
 	else if (pow2 && spaced)
-		BTLBF_PLAUNCH_W(true, true);
+		kernel = pass_a_kernel<H, Q, true, true>(window, overlapped, aux);
 	else
-		BTLBF_PLAUNCH_W(false, true);
-#undef BTLBF_PLAUNCH_W
-#undef BTLBF_PLAUNCH
-	return hipGetLastError();
+		kernel = pass_a_kernel<H, Q, false, true>(window, overlapped, aux);
+	return part_launch(kernel, dim3(out.regions), dim3(kPartThreads), dyn, s, a, out, bin_shift, sd);
 }
 
 

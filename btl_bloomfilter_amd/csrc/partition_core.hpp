@@ -17,6 +17,17 @@ static constexpr uint32_t kStageEntries = 32768; // LDS staging: 128 KiB of uint
 static constexpr uint32_t kFlushItems = kStageEntries / kChunk; // chunks the rings can hold = most one round flushes
 static constexpr uint32_t kPartLdsBudget = 160 * 1024 - 1664; // dynamic LDS a workgroup may ask for (static: SeqShared + the overlapped schedule's handover words, 1600 bytes)
 
+// Host: launch a partition kernel that needs `dyn` bytes of dynamic LDS (more than a kernel gets without asking).
+template <class... P, class... A>
+static hipError_t part_launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t dyn, hipStream_t s, const A&... args)
+{
+	hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
+	if (e != hipSuccess)
+		return e;
+	hipLaunchKernelGGL(kernel, grid, block, dyn, s, args...);
+	return hipGetLastError();
+}
+
 // LDS image of the staged partitioner (carved from dynamic LDS by the kernels)
 struct PartLds {
 	uint32_t* stage;   // [P][SC] ring per bin, SC = kStageEntries / pow2ceil(P)

@@ -642,29 +642,24 @@ hipError_t launch_part_split(void* filter, const PartIn& in, uint32_t first_in, 
 	const size_t dyn = part_lds_bytes(out.P);
 	const uint32_t slices = out.regions;
 	const dim3 grid(n_in_bins * slices);
-#define BTLBF_SLAUNCH(Q, E, PK)                                                                                \
-	do {                                                                                                       \
-		hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&part_split_kernel<Q, E, PK>),        \
-		                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);              \
-		if (e != hipSuccess)                                                                                   \
-			return e;                                                                                          \
-		hipLaunchKernelGGL((part_split_kernel<Q, E, PK>), grid, dim3(kPartThreads), dyn, s, filter, in, out, slices, \
-		                   sub_shift, in_shift, first_in, abs_first - first_in, sd);                            \
-	} while (0)
-	if (out.packed && query)
-		BTLBF_SLAUNCH(true, false, true);
-	else if (out.packed)
-		BTLBF_SLAUNCH(false, false, true);
-	else if (query && exact)
-		BTLBF_SLAUNCH(true, true, false);
-	else if (query)
-		BTLBF_SLAUNCH(true, false, false);
-	else if (exact)
-		BTLBF_SLAUNCH(false, true, false);
-	else
-		BTLBF_SLAUNCH(false, false, false);
-#undef BTLBF_SLAUNCH
-	return hipGetLastError();
+	// <QUERY, EXACT, PK>
+	auto* kernel = out.packed ? (query ? &part_split_kernel<true, false, true> : &part_split_kernel<false, false, true>)
+	               : query    ? (exact ? &part_split_kernel<true, true, false> : &part_split_kernel<true, false, false>)
+	                          : (exact ? &part_split_kernel<false, true, false> : &part_split_kernel<false, false, false>);
+	return part_launch(kernel, grid, dim3(kPartThreads), dyn, s, filter, in, out, slices, sub_shift, in_shift, first_in,
+	                   abs_first - first_in, sd);
+}
+
+// pass C with NT threads per segment: bit filters take packed or unpacked chunks, counting filters unpacked ones
+template <int NT>
+static auto apply_kernel(int mode, bool packed) -> decltype(&part_apply_kernel<APPLY_BIT_OR, NT, false>)
+{
+	switch (mode) {
+	case APPLY_BIT_OR: return packed ? &part_apply_kernel<APPLY_BIT_OR, NT, true> : &part_apply_kernel<APPLY_BIT_OR, NT, false>;
+	case APPLY_BIT_TEST: return packed ? &part_apply_kernel<APPLY_BIT_TEST, NT, true> : &part_apply_kernel<APPLY_BIT_TEST, NT, false>;
+	case APPLY_CNT_INC: return &part_apply_kernel<APPLY_CNT_INC, NT, false>;
+	default: return &part_apply_kernel<APPLY_CNT_TEST, NT, false>;
+	}
 }
 
 hipError_t launch_part_apply(void* filter, uint64_t local_bytes, uint32_t seg_shift, uint64_t seg_first, uint64_t n_seg,
@@ -676,63 +671,29 @@ hipError_t launch_part_apply(void* filter, uint64_t local_bytes, uint32_t seg_sh
 		return hipErrorInvalidValue;
 	const int mode = (sd.counting ? APPLY_CNT_INC : APPLY_BIT_OR) + (query ? 1 : 0);
 	const size_t dyn = (size_t)1 << (seg_shift - (sd.counting ? 0 : 3)); // bytes of one segment
-#define BTLBF_ALAUNCH(M, NT, PK)                                                                                 \
-	do {                                                                                                       \
-		hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&part_apply_kernel<M, NT, PK>),       \
-		                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);              \
-		if (e != hipSuccess)                                                                                   \
-			return e;                                                                                          \
-		hipLaunchKernelGGL((part_apply_kernel<M, NT, PK>), dim3((unsigned)n_seg), dim3(NT), dyn, s,            \
-		                   static_cast<uint8_t*>(filter), local_bytes, seg_shift, (uint32_t)seg_first, in, sd); \
-	} while (0)
-#define BTLBF_ALAUNCH_M(NT)                                 \
-	do {                                                    \
-		switch (mode) {                                     \
-		case APPLY_BIT_OR:                                  \
-			if (in.packed)                                  \
-				BTLBF_ALAUNCH(APPLY_BIT_OR, NT, true);      \
-			else                                            \
-				BTLBF_ALAUNCH(APPLY_BIT_OR, NT, false);     \
-			break;                                          \
-		case APPLY_BIT_TEST:                                \
-			if (in.packed)                                  \
-				BTLBF_ALAUNCH(APPLY_BIT_TEST, NT, true);    \
-			else                                            \
-				BTLBF_ALAUNCH(APPLY_BIT_TEST, NT, false);   \
-			break;                                          \
-		case APPLY_CNT_INC:                                 \
-			BTLBF_ALAUNCH(APPLY_CNT_INC, NT, false);        \
-			break;                                          \
-		default:                                            \
-			BTLBF_ALAUNCH(APPLY_CNT_TEST, NT, false);       \
-			break;                                          \
-		}                                                   \
-	} while (0)
-	if (dyn > 64 * 1024) // 128 KiB segments: one workgroup per CU
-		BTLBF_ALAUNCH_M(1024);
-	else
-		BTLBF_ALAUNCH_M(512);
-#undef BTLBF_ALAUNCH_M
-#undef BTLBF_ALAUNCH
-	return hipGetLastError();
+	const bool wide = dyn > 64 * 1024; // 128 KiB segments: one workgroup of 1024 threads per CU
+	return part_launch(wide ? apply_kernel<1024>(mode, in.packed) : apply_kernel<512>(mode, in.packed), dim3((unsigned)n_seg),
+	                   dim3(wide ? 1024 : 512), dyn, s, static_cast<uint8_t*>(filter), local_bytes, seg_shift, (uint32_t)seg_first,
+	                   in, sd);
 }
 
 // ---- failed-position set (partitioned query, resolve step) ----------------------------------------
 // open-addressing table of 64-bit keys (position + 1; 0 = empty), linear probing
+__device__ __forceinline__ void failset_insert(unsigned long long* table, uint64_t mask, unsigned long long key)
+{
+	uint64_t slot = mix64(key) & mask;
+	for (;;) {
+		const unsigned long long prev = atomicCAS(&table[slot], 0ull, key);
+		if (prev == 0ull || prev == key)
+			break;
+		slot = (slot + 1) & mask;
+	}
+}
 __global__ __launch_bounds__(256) void failset_build_kernel(const uint64_t* list, uint64_t n,
                                                            unsigned long long* table, uint64_t mask)
 {
-	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-	     i += (uint64_t)gridDim.x * blockDim.x) {
-		const unsigned long long key = list[i] + 1;
-		uint64_t slot = mix64(key) & mask;
-		for (;;) {
-			const unsigned long long prev = atomicCAS(&table[slot], 0ull, key);
-			if (prev == 0ull || prev == key)
-				break;
-			slot = (slot + 1) & mask;
-		}
-	}
+	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+		failset_insert(table, mask, list[i] + 1);
 }
 
 hipError_t launch_failset_build(const uint64_t* fail_list, uint64_t n, uint64_t* table, uint64_t mask,
@@ -772,16 +733,8 @@ __global__ __launch_bounds__(256) void failset_build_auto_kernel(const uint64_t*
 	if ((uint32_t)ctl[1] != GATE_RESOLVE)
 		return;
 	const uint64_t n = ctl[1] >> 32, mask = ctl[0];
-	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-		const unsigned long long key = list[i] + 1;
-		uint64_t slot = mix64(key) & mask;
-		for (;;) {
-			const unsigned long long prev = atomicCAS(&table[slot], 0ull, key);
-			if (prev == 0ull || prev == key)
-				break;
-			slot = (slot + 1) & mask;
-		}
-	}
+	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+		failset_insert(table, mask, list[i] + 1);
 }
 
 hipError_t launch_failset_auto(const uint64_t* fail_list, const unsigned long long* fail_count, uint64_t fail_cap,

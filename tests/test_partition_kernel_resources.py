@@ -2,37 +2,13 @@
 their unpacked counterparts do: a 1024-thread workgroup needs at most 128 vector registers per lane, and a spill to
 scratch would cost the bytes the format saves.  hipcc cross-compiles without a GPU, so the compiler's own
 kernel-resource remarks are checked, as tests/test_kernel_resources.py does for pass A."""
-import os
-import re
-import subprocess
-
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "btl_bloomfilter_amd", "csrc", "partition_kernels.hip")
+from kres_util import kernel_resources
 
 
 @pytest.fixture(scope="module")
 def remarks(tmp_path_factory):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    assert os.path.exists(hipcc), "hipcc is part of the image: the build check needs it too"
-    obj = tmp_path_factory.mktemp("kres") / "partition_kernels.o"
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-function",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", "-o", str(obj), SRC],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    out, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()
-            cur = re.sub(r"\(.*", "", cur).replace("void ", "").replace("btlbf::", "")
-            out[cur] = {}
-        for key, pat in (("vgpr", r" VGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)")):
-            m = re.search(pat, line)
-            if m and cur:
-                out[cur][key] = int(m.group(1))
-    return out
+    return kernel_resources("partition_kernels.hip", tmp_path_factory.mktemp("kres") / "partition_kernels.o")
 
 
 # part_split_kernel<QUERY, EXACT, PK>, part_apply_kernel<MODE, NT, PK> (MODE 0 = bit OR, 1 = bit test)
