@@ -1,9 +1,9 @@
 // csrc/host_internal.hpp -- what the host units of the C ABI share, and only that: error plumbing, the filter object,
 // its cached device scratch (DevScratch, PinScratch) and its lazy-clear protocol, the staging pool and the mailbox, parameter
-// blocks, sequence views, and the entry of the sequence path into the partitioned pipeline.  Defined in: capi.cpp
+// blocks, sequence views, and the entries of the sequence path into the partitioned pipeline.  Defined in: capi.cpp
 // (errors, clear protocol, dev_pool, mailbox, parameter blocks, make_filter, views), host_seq.cpp (seq_precheck),
-// host_partition.cpp (the pipeline; its planner's types are private to it), host_aux.cpp (rank_build).  fastx.cpp uses
-// btlbf_set_error alone.
+// host_partition.cpp (the pipeline; its planner's types are in host_partition.hpp, for host_query.cpp alone),
+// host_query.cpp (contains_routed), host_aux.cpp (rank_build).  fastx.cpp uses btlbf_set_error alone.
 #pragma once
 #include "../../include/btlbf.h"
 #include "internal.hpp"
@@ -445,13 +445,17 @@ struct InBuf : private OutBuf {
 	}
 };
 
-// the sequence path enters the partitioned pipeline through these (host_partition.cpp)
+// the sequence path enters the partitioned pipeline through these: inserts (host_partition.cpp) ...
 bool want_partitioned(const btlbf_filter* f, uint64_t len, int counting_op = -1);
 int partitioned_insert(btlbf_filter* f, const SeqArgs& base, hipStream_t s, bool* done);
-int partitioned_contains(btlbf_filter* f, const SeqArgs& base, uint8_t* hit_bits, uint8_t* valid_bits,
-                         uint64_t* counts, hipStream_t s, bool* done, bool defer_hit_count = false);
-int want_partitioned_query(btlbf_filter* f, const SeqArgs& base, hipStream_t s, bool* yes);
-int split_contains(btlbf_filter* f, const SeqArgs& a, int direct_op, hipStream_t s, int* decided);
+
+// ... and contains() (host_query.cpp).  The ways one call can be answered: the direct kernel over the whole buffer; the
+// partitioned pipeline over the whole buffer; uniform reads sampled one by one, the warm ones partitioned in place under
+// a read mask and only the cold ones gathered for the direct kernel (SplitCold), or both compacted (SplitWarm)
+enum class QueryRoute { Direct, Partitioned, SplitCold, SplitWarm };
+// contains() of `a` by the route AUTO / the query mode picks; *answered = false: nothing was written, the caller
+// launches the direct kernel `op` over the whole buffer
+int contains_routed(btlbf_filter* f, const SeqArgs& a, int op, hipStream_t s, bool* answered);
 
 // The rank structure of a whole bit filter (host_aux.cpp): *d_il gets n_blocks records of 9 uint64_t, which the caller
 // owns, and *ones the popcount.  After an allocation that failed *d_il is null; after a build that failed it is not.

@@ -1,15 +1,17 @@
 // csrc/host_partition.cpp -- the partitioned pipeline on the host side: planning (segments, levels, caps, scratch),
-// the partitioned insert and query, the split query, and the multi-GPU routing entry points over the same planner.
+// the partitioned insert and query, and the multi-GPU routing entry points over the same planner.
 //
-// A call plans once and passes the plan down: part_prepare (PartPrep) for the single-GPU pipeline -- the split query
-// hands it the level-0 plan it has already made --, plan_routed (RoutePlan) for the routing entry points.  The plan
-// types, the fail-list constants, the named rules (local_probes, worth_sweep, direct_query_op, part_side) and every
-// plan_* function are private to this unit; the sequence path (host_seq.cpp) enters through want_partitioned,
-// partitioned_insert, partitioned_contains, want_partitioned_query and split_contains (host_internal.hpp).  The
-// scratch lives in the filter's three DevScratch buffers.  Kernels: partition_kernels.hip, part_hash_inst.hip.
+// A call plans once and passes the plan down: part_prepare (PartPrep) for the single-GPU pipeline -- the SplitCold
+// route of a query hands it the level-0 plan it has already made --, plan_routed (RoutePlan) for the routing entry
+// points.  The fail-list constants, the named rules and every plan_* function are private to this unit, except what
+// the query routing (host_query.cpp) decides and executes with: that is declared in host_partition.hpp, which only
+// these two units include.  The sequence path (host_seq.cpp) enters through want_partitioned and partitioned_insert
+// (host_internal.hpp) and, for queries, through host_query.cpp's contains_routed.  The scratch lives in the filter's
+// DevScratch buffers.  Kernels: partition_kernels.hip, part_hash_inst.hip.
 #include "../../include/btlbf.h"
 #include "internal.hpp"
 #include "host_internal.hpp"
+#include "host_partition.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -26,58 +28,6 @@ static constexpr uint64_t kFailCap = 4ull << 20;          // entries
 static constexpr uint64_t kFailTableSlots = 2 * kFailCap; // power of two
 // entries a FRESH insert batch (partitioned_insert) may report as explicit positions instead of staging them
 static constexpr uint64_t kFreshSpillCap = 16ull << 20;
-
-// The tail of the partition scratch: a query's fail list + failed-position table, or a fresh insert's spill list.
-// Inserts (fresh or not) and queries reserve the same tail, so that alternating between them never changes the
-// scratch size (a re-allocation of ~100 GB costs seconds); a caller-imposed budget below 2 GiB gets short lists
-// (more than a list holds and the batch is redone the plain way, which is always correct).
-struct PartTail {
-	uint64_t fail_cap, table_slots, spill_cap, bytes;
-};
-static PartTail part_tail(uint64_t budget)
-{
-	PartTail t;
-	const bool full = budget >= (2ull << 30);
-	t.fail_cap = full ? kFailCap : 256ull << 10;
-	t.spill_cap = full ? kFreshSpillCap : 512ull << 10;
-	t.table_slots = 2 * t.fail_cap;
-	t.bytes = std::max<uint64_t>(256 + t.fail_cap * 8 + t.table_slots * 8, 256 + t.spill_cap * 8);
-	return t;
-}
-
-// one partition level: bins of 2^shift positions, written as regions of `cap` chunks
-struct PartLevel {
-	uint32_t bins = 0;    // bins at this level (covering the local array)
-	uint32_t P = 0;       // bins per writer block (pass A: all of them; split: the fan-out)
-	uint32_t regions = 0; // writers per bin
-	uint32_t cap = 0;     // chunks per region
-	uint32_t shift = 0;   // log2(positions per bin)
-	uint32_t wseg = 0;    // level 0 only: bins of `wseg` segments each instead (plan_level0); `shift` is then unused
-	uint32_t alloc_bins = 0; // bins the arrays hold at a time (== bins unless the level is processed in groups)
-	uint32_t packed = 0;  // its chunks hold kPackChunk packed entries, not kChunk words (plan_caps decides)
-	uint64_t cnt_bytes = 0, ent_bytes = 0;
-	uint32_t* cnt = nullptr;
-	uint32_t* ent = nullptr;
-	PartOut out() const { return PartOut{P, regions, cap, packed, cnt, ent}; }
-	PartIn in() const { return PartIn{1, alloc_bins, regions, cap, cnt, ent, packed}; }
-};
-
-struct PartPlan {
-	uint32_t seg_shift = 19;
-	uint64_t n_seg = 0;
-	bool counting = false;   // the array holds counters: every level keeps 32-bit entries (plan_segments)
-	uint32_t group_bins = 0; // level-0 bins split + applied together (one-split plans); 0 = all at once
-	int n_levels = 0; // lv[0] = pass A output (or the exchanged data), lv[1..] = split outputs
-	PartLevel lv[3];
-	uint64_t tiles_per_batch = 0;
-	uint64_t bytes_total = 0;
-	// pass A's overlapped schedule keeps the entries that find their ring full in a late image per workgroup and
-	// round parity (part_hash_inst.hip): [regions][2][late_cap] words behind the tail of the scratch
-	uint32_t* late_buf = nullptr;
-	uint32_t late_cap = 0;
-	// level-0 bins that are split and applied together, of the n_bins0 a pass has (plans without groups: all of them)
-	uint32_t group(uint32_t n_bins0) const { return n_levels >= 2 && group_bins ? group_bins : n_bins0; }
-};
 
 // chunks a region needs for `mean_entries` expected entries (Poisson: mean + 8 sigma) plus the
 // partially filled chunk flushed at kernel end
@@ -229,16 +179,6 @@ uint8_t* carve_levels(PartPlan& pl, uint8_t* p, int first_level)
 	return p;
 }
 
-uint64_t scratch_budget(btlbf_filter* f)
-{
-	if (f->part_budget)
-		return f->part_budget;
-	size_t free_b = 0, total_b = 0;
-	if (hipMemGetInfo(&free_b, &total_b) != hipSuccess)
-		return 0;
-	return (uint64_t)((double)(free_b + f->part.bytes) * 0.80);
-}
-
 unsigned cu_count(int device)
 {
 	int cus = 256;
@@ -325,9 +265,35 @@ int run_levels(btlbf_filter* f, PartPlan& pl, PartIn in0, const PartSide& sd, in
 // atomics/s), the partitioned one 26.5 ms + 1.9 ms per 10^6 reads -- equal at 0.82 %; the direct query 9.3 ms per 10^6
 // reads (all hits: four gathers per k-mer), the partitioned one 17.3 ms + 1.6 per 10^6 -- equal at 1.57 %.  (Round 2's
 // rule was 2 % for both: a batch of 2x10^6 reads was inserted in 48.7 ms instead of 30.4.)
-constexpr double kAutoInsertRatio = 0.0095, kAutoQueryRatio = 0.0165;
+constexpr double kAutoInsertRatio = 0.0095; // (kAutoQueryRatio = 0.0165: host_partition.hpp)
 // plan_level0: calls of this many probes or more (4x10^9 k-mers at h = 4) take 256 level-0 bins where 512 are the rule
 constexpr double kWideSplitProbes = 1.6e10;
+
+} // namespace
+
+// ---- what the query routing shares (host_partition.hpp) ---------------------------------------------------------
+namespace btlbf {
+
+PartTail part_tail(uint64_t budget)
+{
+	PartTail t;
+	const bool full = budget >= (2ull << 30);
+	t.fail_cap = full ? kFailCap : 256ull << 10;
+	t.spill_cap = full ? kFreshSpillCap : 512ull << 10;
+	t.table_slots = 2 * t.fail_cap;
+	t.bytes = std::max<uint64_t>(256 + t.fail_cap * 8 + t.table_slots * 8, 256 + t.spill_cap * 8);
+	return t;
+}
+
+uint64_t scratch_budget(btlbf_filter* f)
+{
+	if (f->part_budget)
+		return f->part_budget;
+	size_t free_b = 0, total_b = 0;
+	if (hipMemGetInfo(&free_b, &total_b) != hipSuccess)
+		return 0;
+	return (uint64_t)((double)(free_b + f->part.bytes) * 0.80);
+}
 
 // probes a call over `len` bases sends to this filter's local array (a shard keeps its window's share)
 double local_probes(const btlbf_filter* f, uint64_t len)
@@ -359,7 +325,7 @@ double call_probes(const btlbf_filter* f, uint64_t len)
 
 // the segment size and the level-0 bins (pass A's output) of this filter's local array; false = no partitioned path
 // `call_probes`: probes of the whole call (0 = unknown), for the one choice that depends on the batch size
-bool plan_level0(const btlbf_filter* f, PartPlan& pl, double call_probes = 0)
+bool plan_level0(const btlbf_filter* f, PartPlan& pl, double call_probes)
 {
 	if (!plan_segments(f->mod.shard_len, pl, f->kind == BTLBF_COUNTING8 ? 0 : 3))
 		return false;
@@ -402,6 +368,10 @@ bool plan_level0(const btlbf_filter* f, PartPlan& pl, double call_probes = 0)
 	l0.alloc_bins = l0.bins;
 	return true;
 }
+
+} // namespace btlbf
+
+namespace {
 
 // what part_prepare makes of a buffer
 struct PartPrep {
@@ -687,10 +657,9 @@ int partitioned_insert(btlbf_filter* f, const SeqArgs& base, hipStream_t s, bool
 // cache-resident hash set and one more hashing pass clears the windows that own one of them.  Too
 // many failures (a miss-heavy batch) and the batch is redone by the direct gather kernel.
 // hit_bits (device) is required; valid_bits and counts are optional.
-// base.read_mask (the split query): those reads are left out -- no bits, no counts; defer_hit_count: counts[1] is left
-// for the caller, who adds the left-out reads' answers to the bitmap first.
-// `level0`: see part_prepare
-static int part_query(btlbf_filter* f, const SeqArgs& base, uint8_t* hit_bits, uint8_t* valid_bits, uint64_t* counts,
+// base.read_mask, defer_hit_count and level0 (see part_prepare) serve the SplitCold route alone and are described at its
+// call (host_query.cpp).
+int part_query(btlbf_filter* f, const SeqArgs& base, uint8_t* hit_bits, uint8_t* valid_bits, uint64_t* counts,
                hipStream_t s, bool* done, bool defer_hit_count, const PartPlan* level0)
 {
 	*done = false;
@@ -754,309 +723,6 @@ static int part_query(btlbf_filter* f, const SeqArgs& base, uint8_t* hit_bits, u
 		                        reinterpret_cast<unsigned long long*>(counts) + 1, s));
 	*done = true;
 	return BTLBF_OK;
-}
-
-int partitioned_contains(btlbf_filter* f, const SeqArgs& base, uint8_t* hit_bits, uint8_t* valid_bits,
-                         uint64_t* counts, hipStream_t s, bool* done, bool defer_hit_count)
-{
-	return part_query(f, base, hit_bits, valid_bits, counts, s, done, defer_hit_count, nullptr);
-}
-
-// AUTO decision for contains(): large batch, and a sample of tiles says nearly every k-mer hits
-int want_partitioned_query(btlbf_filter* f, const SeqArgs& base, hipStream_t s, bool* yes)
-{
-	*yes = false;
-	if (f->query_mode == BTLBF_INSERT_DIRECT)
-		return BTLBF_OK;
-	if (!part_supported(f->hp) || base.len == 0)
-		return BTLBF_OK;
-	if (f->query_mode == BTLBF_INSERT_PARTITIONED) {
-		*yes = true;
-		return BTLBF_OK;
-	}
-	const double live = local_probes(f, base.len);
-	if (!worth_sweep(f, live, kAutoQueryRatio))
-		return BTLBF_OK;
-	// sample 64 tiles spread over the buffer with the direct kernel
-	const uint64_t tiles = (base.len + seq_tile_windows() - 1) / seq_tile_windows();
-	const unsigned n_s = (unsigned)std::min<uint64_t>(64, tiles);
-	HIP_TRY(hipMemsetAsync(f->d_scalar, 0, 16, s));
-	for (unsigned i = 0; i < n_s; ++i) {
-		SeqArgs a = base;
-		a.first_tile = (tiles / n_s) * i;
-		a.n_tiles = 1;
-		a.hit_bits = nullptr;
-		a.valid_bits = nullptr;
-		a.counts = reinterpret_cast<uint64_t*>(f->d_scalar);
-		a.min_out = nullptr;
-		HIP_TRY(launch_seq_op(direct_query_op(f), a, s));
-	}
-	unsigned long long c[2] = {0, 0};
-	HIP_TRY(hipMemcpyAsync(c, f->d_scalar, 16, hipMemcpyDeviceToHost, s));
-	HIP_TRY(hipStreamSynchronize(s));
-	if (c[0] == 0)
-		return BTLBF_OK;
-	// expected failed probes in the whole call (at most h per missing k-mer) must stay well below
-	// what the fail list holds per batch
-	const double miss = (double)(c[0] - c[1]) / (double)c[0];
-	*yes = miss * live < 0.25 * (double)part_tail(scratch_budget(f)).fail_cap;
-	return BTLBF_OK;
-}
-
-// ---- the split query: contains() over fixed-length reads in AUTO mode (aux_kernels.hip) ------------------------------
-// what its steps share: the reads' cold flags and their prefix sums (in f->flags) and the counts
-struct SplitState {
-	uint32_t L = 0; // read length
-	uint64_t n_reads = 0;
-	unsigned long long n_cold = 0, *d_ncold = nullptr;
-	uint64_t* d_flags = nullptr;
-	uint32_t* d_prefix = nullptr;
-};
-
-static uint64_t up256(uint64_t x) { return (x + 255) / 256 * 256; }
-
-// the direct kernel over a compacted buffer of the split query: it ADDS its clean windows and its hits to a.counts
-static int split_direct(btlbf_filter* f, const SeqArgs& a, int direct_op, const uint8_t* seq, uint64_t len, uint8_t* hit_bits,
-                        uint8_t* valid_bits, hipStream_t s)
-{
-	SeqArgs d = a;
-	d.seq = seq;
-	d.len = len;
-	d.hit_bits = hit_bits;
-	d.valid_bits = valid_bits;
-	ProfSpan ps(f, BTLBF_PROF_QUERY_DIRECT, s);
-	REQUIRE_MATERIALIZED(f);
-	HIP_TRY(launch_seq_op(direct_op, d, s));
-	return BTLBF_OK;
-}
-
-// The decision: sample the reads; *decided = 0: not applicable (the plain paths decide, want_partitioned_query), 1: the
-// gather kernel, 2: the whole buffer goes partitioned, 3: split -- `st` then holds every read's flag and the cold count.
-static int split_decide(btlbf_filter* f, const SeqArgs& a, hipStream_t s, SplitState& st, int* decided)
-{
-	*decided = 0;
-	const uint32_t L = a.layout.starts ? 0 : a.layout.read_len, k = f->hp.k;
-	// whole filters only: the sampler probes f->d_data with positions of the whole array (a shard answers for its
-	// window through the WINDOW kernels; want_partitioned_query decides for it)
-	if (f->shard_count != 1 || f->mod.shard_lo != 0 || f->mod.shard_len != f->mod.size)
-		return BTLBF_OK;
-	if (f->query_mode != BTLBF_INSERT_AUTO || !L || L < k || L < 8 || f->hp.n_seeds || !part_supported(f->hp))
-		return BTLBF_OK;
-	const uint64_t n_reads = a.len / L;
-	const uint32_t W = L - k + 1;
-	if (!worth_sweep(f, (double)n_reads * W * f->hp.h, kAutoQueryRatio) || n_reads >= (1ull << 32))
-		return BTLBF_OK; // small batches: the direct kernel (want_partitioned_query agrees)
-	const uint64_t n_fw = (n_reads + 63) / 64;
-	// temporaries are cached in the filter (DevScratch): the small one (flags, prefix sums) is needed by every call,
-	// the large one (compacted reads, their bitmaps) only once the split path is taken
-	// (the flags are readable for 256 bytes behind their last word: pass A reads up to 34 words from a tile's first one on)
-	const uint64_t sz_flags = up256(n_fw * 8 + 256), sz_prefix = up256((n_fw + (n_fw + 1023) / 1024 + 1) * 4);
-	if (!f->flags.grow(256 + sz_flags + sz_prefix, f->device))
-		return BTLBF_OK; // no room: the plain paths decide (want_partitioned_query)
-	uint8_t* const base = static_cast<uint8_t*>(f->flags.p);
-	st.L = L;
-	st.n_reads = n_reads;
-	st.d_ncold = reinterpret_cast<unsigned long long*>(base);
-	st.d_flags = reinterpret_cast<uint64_t*>(base + 256);
-	st.d_prefix = reinterpret_cast<uint32_t*>(base + 256 + sz_flags);
-	// what the fail list copes with / what is worth a sweep of the array, in reads
-	// (the list the partitioned path will really have: a small scratch budget gets a short one, part_tail)
-	const double few_cold = 0.25 * (double)part_tail(scratch_budget(f)).fail_cap / ((double)W * f->hp.h);
-	auto sample = [&](uint32_t stride, uint32_t probes2) -> int { // flags and st.n_cold from every stride-th read
-		HIP_TRY(hipMemsetAsync(st.d_ncold, 0, 8, s));
-		{
-			ProfSpan ps(f, BTLBF_PROF_QUERY_RESOLVE, s);
-			HIP_TRY(launch_read_sample(a.seq, n_reads, L, stride, f->hp, f->mod, f->d_data, f->kind == BTLBF_COUNTING8,
-			                           f->thr, st.d_flags, reinterpret_cast<uint64_t*>(st.d_ncold), s, probes2));
-		}
-		HIP_TRY(hipMemcpyAsync(&st.n_cold, st.d_ncold, 8, hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		return BTLBF_OK;
-	};
-	auto warm_too_few = [&](double n_warm_reads) { return !worth_sweep(f, n_warm_reads * W * f->hp.h, kAutoQueryRatio); };
-	// 1. an estimate from one read in 64: all-hit and all-miss buffers -- the common cases -- are recognised at
-	//    1/64 of the cost of looking at every read
-	const uint32_t stride = n_reads >= (1u << 20) ? 64 : 1;
-	double cold_frac = 1.0; // estimate from the first look (unknown: assume many)
-	if (stride > 1) {
-		if (int rc = sample(stride, 0))
-			return rc;
-		const uint64_t n_s = (n_reads + stride - 1) / stride;
-		cold_frac = (double)st.n_cold / (double)n_s;
-		if (st.n_cold == 0 && (double)n_reads * 8.0 / (double)n_s < few_cold) { // none in the sample: few overall
-			*decided = 2;
-			return BTLBF_OK;
-		}
-		if (warm_too_few((double)(n_s - st.n_cold) * stride * 1.5)) {
-			*decided = 1;
-			return BTLBF_OK;
-		}
-	}
-	// 2. every read.  A present read costs the sampler its probes (they all hit, so they are all loaded), and the second
-	//    sample only has to keep a foreign read from passing on ONE false-positive window: with few foreign reads, fewer
-	//    of its probes do (a read that passes all the same costs a resolve pass, never a wrong answer)
-	const uint32_t h = f->hp.h;
-	const uint32_t probes2 = cold_frac <= 0.0025 ? (h + 1) / 2 : cold_frac <= 0.025 ? std::max((h + 1) / 2, h - 1) : h;
-	if (int rc = sample(1, probes2))
-		return rc;
-	// the fail list copes with that many misses: 2; the warm reads are not worth a sweep of the array: 1; else split
-	*decided = (double)st.n_cold < few_cold ? 2 : warm_too_few((double)(n_reads - st.n_cold)) ? 1 : 3;
-	return BTLBF_OK;
-}
-
-// carve f->split into n buffers of sz[i] bytes (0: none); returns what they take together
-static uint64_t split_carve(const btlbf_filter* f, const uint64_t* sz, uint8_t** q, int n)
-{
-	uint64_t off = 0;
-	for (int i = 0; i < n; ++i) {
-		q[i] = sz[i] ? static_cast<uint8_t*>(f->split.p) + off : nullptr;
-		off += sz[i];
-	}
-	return off;
-}
-
-// Uniform reads that pass A takes through its read grid (level-0 plan `pl0`): the warm reads stay where they are -- pass
-// A leaves the cold ones out by their flags (zero-staged: no entries, no bits, no counts) --, only the COLD reads are
-// gathered for the direct kernel, and their answers are ORed back into the caller's bitmaps.  The first version gathered
-// the warm reads as well (15 GB copied and 15 GB of HBM that the partition scratch then lacked: a third batch) and
-// merged every word of the bitmaps from two sources.
-static int split_cold_only(btlbf_filter* f, const SeqArgs& a, int direct_op, hipStream_t s, const SplitState& st,
-                           const PartPlan& pl0, int* decided)
-{
-	const uint32_t L = st.L;
-	const uint64_t n_cold = st.n_cold, cold_len = n_cold * L;
-	const bool wv = a.valid_bits != nullptr;
-	const uint64_t szm[5] = {up256(cold_len + 16), up256(bitmap_bytes(cold_len) + 16), wv ? up256(bitmap_bytes(cold_len) + 16) : 0,
-	                         up256(n_cold * 4 + 16), a.hit_bits ? 0 : up256(bitmap_bytes(a.len) + 16)};
-	uint64_t need = 0;
-	for (uint64_t v : szm)
-		need += v;
-	// (a buffer left behind by a call that gathered the warm reads as well -- 19 GB for 10^8 reads -- is given back
-	// first: the partition scratch is planned from the free HBM, and with that much less of it the pass would need
-	// a third batch, i.e. a third sweep of the array)
-	if (f->split.bytes > 4 * need + (1ull << 30))
-		f->split.release();
-	if (!f->split.grow(need, f->device)) {
-		*decided = 1;
-		return BTLBF_OK;
-	}
-	uint8_t* q[5];
-	split_carve(f, szm, q, 5);
-	uint8_t *cold_p = q[0], *cold_hit_p = q[1], *cold_valid_p = q[2];
-	uint32_t* cold_index = reinterpret_cast<uint32_t*>(q[3]);
-	uint8_t* hb = a.hit_bits ? a.hit_bits : q[4];
-	{
-		ProfSpan ps(f, BTLBF_PROF_QUERY_RESOLVE, s);
-		HIP_TRY(launch_flag_prefix(st.d_flags, st.n_reads, st.d_prefix, s));
-		HIP_TRY(launch_gather_cold_reads(a.seq, st.n_reads, L, st.d_flags, st.d_prefix, cold_p, cold_index, s));
-		HIP_TRY(hipMemsetAsync(cold_hit_p + bitmap_bytes(cold_len), 0, 16, s)); // (the merge reads a word further)
-		if (wv)
-			HIP_TRY(hipMemsetAsync(cold_valid_p + bitmap_bytes(cold_len), 0, 16, s));
-	}
-	SeqArgs b = a;
-	b.read_mask = reinterpret_cast<const uint32_t*>(st.d_flags);
-	b.hit_bits = b.valid_bits = nullptr;
-	b.counts = nullptr;
-	bool done_w = false;
-	if (int rc = part_query(f, b, hb, a.valid_bits, a.counts, s, &done_w, true, &pl0))
-		return rc;
-	if (!done_w) { // no room for the partition scratch: the gather kernel answers the whole buffer
-		*decided = 1;
-		return BTLBF_OK;
-	}
-	if (int rc = split_direct(f, a, direct_op, cold_p, cold_len, cold_hit_p, cold_valid_p, s)) // (its hits: recounted below)
-		return rc;
-	{
-		ProfSpan ps(f, BTLBF_PROF_QUERY_RESOLVE, s);
-		HIP_TRY(launch_merge_cold_bitmaps(n_cold, L, cold_index, reinterpret_cast<const uint64_t*>(cold_hit_p),
-		                                  reinterpret_cast<const uint64_t*>(cold_valid_p), reinterpret_cast<uint64_t*>(hb),
-		                                  reinterpret_cast<uint64_t*>(a.valid_bits), s));
-		if (a.counts) { // hits = set bits of the finished bitmap
-			HIP_TRY(hipMemsetAsync(a.counts + 1, 0, 8, s));
-			HIP_TRY(launch_popcount(hb, bitmap_bytes(a.len), 0, 0, reinterpret_cast<unsigned long long*>(a.counts) + 1, s));
-		}
-	}
-	*decided = 3;
-	return BTLBF_OK;
-}
-
-// The reads are compacted into a warm and a cold buffer, the warm one takes the partitioned path (a buffer of its own
-// length, planned for itself), the cold one the early-exit gather kernel, and the two bitmaps are merged back into the
-// caller's layout.
-static int split_warm_cold(btlbf_filter* f, const SeqArgs& a, int direct_op, hipStream_t s, const SplitState& st, int* decided)
-{
-	const uint32_t L = st.L;
-	const uint64_t warm_len = (st.n_reads - st.n_cold) * L, cold_len = st.n_cold * L;
-	const bool wv = a.valid_bits != nullptr;
-	const uint64_t sz[6] = {up256(warm_len + 16), up256(cold_len + 16), up256(bitmap_bytes(warm_len) + 16),
-	                        up256(bitmap_bytes(cold_len) + 16), wv ? up256(bitmap_bytes(warm_len) + 16) : 0,
-	                        wv ? up256(bitmap_bytes(cold_len) + 16) : 0};
-	// sized for any split of a buffer this long, so that the next call's ratio does not move memory
-	const uint64_t worst = up256(a.len + 32) + 512 + (wv ? 2 : 1) * (up256(bitmap_bytes(a.len) + 32) + 512);
-	if (!f->split.grow(worst, f->device)) {
-		*decided = 1; // no room for the compacted copies: the gather kernel answers any mix
-		return BTLBF_OK;
-	}
-	uint8_t* bufs[6];
-	if (split_carve(f, sz, bufs, 6) > f->split.bytes)
-		return fail(BTLBF_EINVAL, "split query: buffer arithmetic");
-	uint8_t *warm_p = bufs[0], *cold_p = bufs[1], *warm_hit_p = bufs[2], *cold_hit_p = bufs[3], *warm_valid_p = bufs[4],
-	        *cold_valid_p = bufs[5];
-	{
-		ProfSpan ps(f, BTLBF_PROF_QUERY_RESOLVE, s);
-		HIP_TRY(launch_flag_prefix(st.d_flags, st.n_reads, st.d_prefix, s));
-		HIP_TRY(launch_compact_reads(a.seq, st.n_reads, L, st.d_flags, st.d_prefix, warm_p, cold_p, s));
-		// the merge reads one word past the last bit of a compacted bitmap
-		HIP_TRY(hipMemsetAsync(warm_hit_p + bitmap_bytes(warm_len), 0, 16, s));
-		HIP_TRY(hipMemsetAsync(cold_hit_p + bitmap_bytes(cold_len), 0, 16, s));
-		if (a.valid_bits) {
-			HIP_TRY(hipMemsetAsync(warm_valid_p + bitmap_bytes(warm_len), 0, 16, s));
-			HIP_TRY(hipMemsetAsync(cold_valid_p + bitmap_bytes(cold_len), 0, 16, s));
-		}
-	}
-	if (a.counts)
-		HIP_TRY(hipMemsetAsync(a.counts, 0, 16, s));
-	SeqArgs b = a;
-	b.seq = warm_p;
-	b.len = warm_len;
-	b.hit_bits = b.valid_bits = nullptr;
-	b.counts = nullptr;
-	bool done_w = false;
-	if (int rc = part_query(f, b, warm_hit_p, warm_valid_p, a.counts, s, &done_w, false, nullptr))
-		return rc;
-	int rc = BTLBF_OK;
-	if (!done_w) // no room for the partition scratch: the gather kernel does the warm reads too
-		rc = split_direct(f, a, direct_op, warm_p, warm_len, warm_hit_p, warm_valid_p, s);
-	if (rc || (rc = split_direct(f, a, direct_op, cold_p, cold_len, cold_hit_p, cold_valid_p, s)))
-		return rc;
-	if (a.hit_bits || a.valid_bits) {
-		ProfSpan ps(f, BTLBF_PROF_QUERY_RESOLVE, s);
-		HIP_TRY(launch_merge_split_bitmaps(a.len, L, st.d_flags, st.d_prefix, reinterpret_cast<uint64_t*>(warm_hit_p),
-		                                   reinterpret_cast<uint64_t*>(cold_hit_p), reinterpret_cast<uint64_t*>(warm_valid_p),
-		                                   reinterpret_cast<uint64_t*>(cold_valid_p), reinterpret_cast<uint64_t*>(a.hit_bits),
-		                                   reinterpret_cast<uint64_t*>(a.valid_bits), s));
-	}
-	*decided = 3;
-	return BTLBF_OK;
-}
-
-// Sample every read (split_decide); if the misses are few enough for the fail list the whole buffer goes partitioned
-// (*decided = 2), if hardly anything hits it goes to the gather kernel (1); otherwise the warm reads take the partitioned
-// path and the cold ones the gather kernel, by one of the two executors above (3: a.hit_bits / a.valid_bits / a.counts
-// are complete).
-int split_contains(btlbf_filter* f, const SeqArgs& a, int direct_op, hipStream_t s, int* decided)
-{
-	SplitState st;
-	int rc = split_decide(f, a, s, st, decided);
-	if (rc || *decided != 3)
-		return rc;
-	// (up to a quarter of the reads cold: beyond that the lanes pass A spends on zero-staged reads cost more than
-	// gathering the warm reads costs -- at one read in two 76 instead of 43 ms of pass A per 10^8 reads)
-	PartPlan pl0; // level 0 is planned here, once: the partitioned query takes it over (the grid belongs to its geometry)
-	PartGrid g;
-	if (4 * st.n_cold <= st.n_reads && plan_level0(f, pl0, call_probes(f, a.len)) && part_read_grid(f->hp, pl0.lv[0].P, a.layout, &g))
-		return split_cold_only(f, a, direct_op, s, st, pl0, decided);
-	return split_warm_cold(f, a, direct_op, s, st, decided);
 }
 
 } // namespace btlbf

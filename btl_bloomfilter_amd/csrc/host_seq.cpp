@@ -1,8 +1,10 @@
 // csrc/host_seq.cpp -- the compute entry points over sequences, precomputed hash rows and raw k-mers.
 //
 // run_query_like is the hot path of every query flavour: the mailbox fast path for a short host sequence, else staged
-// buffers and the choice between the direct kernels and the partitioned pipeline (host_partition.cpp, entered through
-// the five functions host_internal.hpp declares).
+// buffers and, for contains(), the routed query (host_query.cpp's contains_routed, which picks between the direct
+// kernels, the partitioned pipeline and the split routes); what it leaves unanswered, and every other flavour, is the one
+// whole-buffer launch of the direct kernel here.  Inserts enter the partitioned pipeline (host_partition.cpp) through
+// want_partitioned and partitioned_insert.
 #include "../../include/btlbf.h"
 #include "internal.hpp"
 #include "host_internal.hpp"
@@ -110,34 +112,12 @@ int run_query_like(btlbf_filter* f, int op, const char* seq, uint64_t len, const
 	a.valid_bits = static_cast<uint8_t*>(ob_valid.d);
 	a.counts = static_cast<uint64_t*>(ob_cnt.d);
 	a.min_out = static_cast<uint8_t*>(ob_min.d);
-	bool done = false;
+	bool answered = false;
 	if (op == OP_BF_CONTAINS || op == OP_BF_CONTAINS_WIN || (op == OP_CBF_QUERY && !min_out)) { // minimum counts need the values: direct
-		bool yes = false;
-		int decided = 0; // split_contains: 0 = not applicable, 1 = direct, 2 = partitioned, 3 = done
-		if (op != OP_BF_CONTAINS_WIN && (rc = split_contains(f, a, op, s, &decided)))
+		if ((rc = contains_routed(f, a, op, s, &answered)))
 			return rc;
-		done = decided == 3;
-		yes = decided == 2;
-		if (decided == 0 && (rc = want_partitioned_query(f, a, s, &yes)))
-			return rc;
-		if (yes) {
-			DevBuf tmp_hit; // the partitioned path needs a hit bitmap to refine even if the caller wants counts only
-			uint8_t* hb = a.hit_bits;
-			if (!hb) {
-				HIP_TRY(tmp_hit.alloc(bitmap_bytes(len) + 16));
-				hb = tmp_hit.as<uint8_t>();
-			}
-			SeqArgs b = a;
-			b.hit_bits = nullptr;
-			b.valid_bits = nullptr;
-			b.counts = nullptr;
-			if ((rc = partitioned_contains(f, b, hb, a.valid_bits, a.counts, s, &done)))
-				return rc;
-			if (done && !a.hit_bits)
-				HIP_TRY(hipStreamSynchronize(s)); // tmp_hit is freed on return
-		}
 	}
-	if (!done) {
+	if (!answered) {
 		REQUIRE_MATERIALIZED(f);
 		ProfSpan ps(f, op == OP_BF_CONTAINS || op == OP_BF_CONTAINS_WIN ? BTLBF_PROF_QUERY_DIRECT : BTLBF_PROF_OTHER, s);
 		HIP_TRY(launch_seq_op(op, a, s));
@@ -246,6 +226,17 @@ int run_kmer_rows(btlbf_filter* f, int hop, const char* kmers, uint64_t n, uint8
 	return BTLBF_OK;
 }
 
+// try the partitioned insert of `a`; *done: it ran, and a call from host memory has waited for it (false: the scratch does
+// not fit, nothing was launched, the caller goes on to the direct kernels)
+int try_partitioned_insert(btlbf_filter* f, const SeqArgs& a, int mem, hipStream_t s, bool* done)
+{
+	if (int rc = partitioned_insert(f, a, s, done))
+		return rc;
+	if (*done && mem == BTLBF_HOST)
+		HIP_TRY(hipStreamSynchronize(s));
+	return BTLBF_OK;
+}
+
 } // namespace
 
 extern "C" int btlbf_insert_seqs(btlbf_filter* f, const char* seq, uint64_t len,
@@ -267,14 +258,8 @@ extern "C" int btlbf_insert_seqs(btlbf_filter* f, const char* seq, uint64_t len,
 		kop = OP_BF_INSERT; // bit OR is order-free: serial order would give the same bytes
 		if (want_partitioned(f, len)) {
 			bool done = false;
-			rc = partitioned_insert(f, a, s, &done);
-			if (rc)
+			if ((rc = try_partitioned_insert(f, a, mem, s, &done)) || done)
 				return rc;
-			if (done) {
-				if (mem == BTLBF_HOST)
-					HIP_TRY(hipStreamSynchronize(s));
-				return BTLBF_OK;
-			}
 		}
 		MATERIALIZE(f, s);
 	} else {
@@ -288,14 +273,8 @@ extern "C" int btlbf_insert_seqs(btlbf_filter* f, const char* seq, uint64_t len,
 		if (order != BTLBF_ORDER_SERIAL && want_partitioned(f, len, op)) {
 			// incrementAll is order-free up to saturation, which is order-free too: exact in any order
 			bool done = false;
-			rc = partitioned_insert(f, a, s, &done);
-			if (rc)
+			if ((rc = try_partitioned_insert(f, a, mem, s, &done)) || done)
 				return rc;
-			if (done) {
-				if (mem == BTLBF_HOST)
-					HIP_TRY(hipStreamSynchronize(s));
-				return BTLBF_OK;
-			}
 		}
 		MATERIALIZE(f, s);
 		if (order == BTLBF_ORDER_SERIAL) {

@@ -289,7 +289,7 @@ hipError_t launch_count_per_seq(const uint64_t* hit_bits, const uint64_t* valid_
 hipError_t launch_and_answers(const uint64_t* tags, const uint8_t* answers, uint64_t n, uint32_t h,
                               uint64_t* hit_bits, hipStream_t s);
 
-// split query (aux_kernels.hip): per-read sampling, cold-read ranks, compaction, bitmap merge
+// split query (split_query_kernels.hip): per-read sampling, cold-read ranks, compaction, bitmap merge
 hipError_t launch_read_sample(const uint8_t* seq, uint64_t n_reads, uint32_t L, uint32_t stride, const HashParams& hp,
                               const ModParams& mod, const void* filter, int counting, uint32_t threshold, uint64_t* flags,
                               uint64_t* n_cold, hipStream_t s, uint32_t probes2 = 0);

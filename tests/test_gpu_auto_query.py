@@ -1,6 +1,6 @@
-"""contains() over fixed-length reads in AUTO mode -- the sampled decision (split_decide) and its two split executors --
-where it decides: buffers of 2^20 reads and more (the two-stage sampler), counting filters, and the input shapes the
-split path is not given elsewhere.
+"""contains() over fixed-length reads in AUTO mode -- the sampled decision (decide_route, host_query.cpp) and its two
+split routes -- where it decides: buffers of 2^20 reads and more (the two-stage sampler), counting filters, and the
+input shapes the split path is not given elsewhere.
 
 Every case is held against two references at once:
 
@@ -198,7 +198,7 @@ def test_two_stage_sampler_bit_filter(bf, oracle, case1, sub, bits, path, looks)
     non-power-of-two modulo) bits, about 11 % (14 %) full after the N1 inserts: a foreign window is a false positive
     with probability 1.5e-4 (4.4e-4), so foreign reads are sampled cold and inserted reads warm.
 
-    From 2^20 reads on split_decide first looks at one read in 64 -- n_s = 16386 reads -- and derives cold_frac and
+    From 2^20 reads on decide_route first looks at one read in 64 -- n_s = 16386 reads -- and derives cold_frac and
     the second sample's probes from it.  With the 1 GiB scratch cap the fail list has 256 Ki entries and few_cold =
     0.25 * 262144 / (W * h) = 546 reads; with the default budget 4 Mi entries and few_cold = 8738.
 
