@@ -40,7 +40,17 @@
  *      else           : the whole buffer is one sequence
  *    `starts` lives in the same memory space as the sequence buffer.
  *  - per-window results are bitmaps of ceil(len/64) uint64_t words: bit (p & 63) of word p >> 6
- *    belongs to the window starting at byte p; windows that are not clean report 0.
+ *    belongs to the window starting at byte p; windows that are not clean report 0, and so do the bits of
+ *    the last word at positions >= len: every word of a bitmap is defined.
+ *  - output buffers: an output array need not be initialised by the caller.  A call that returns BTLBF_OK has
+ *    stored every byte of every output it was given -- the zeros of unclean windows, of the windows past a
+ *    sequence's last k-mer and of the unused records of a result row included -- and no call writes outside
+ *    [out, out + size) of an output, whether the buffers are host or device memory (malloc'd or reused memory
+ *    is as good as zeroed memory).  A call that returns an error may have written any part of its outputs
+ *    unless its own text says that nothing is written.  Where the content of part of an output is deliberately
+ *    left alone, the call's text says so (btlbf_mibf_frame_probs: frame_probs[0]); running totals that a call
+ *    ADDS to (btlbf_mibf_id_counts, btlbf_mibf_classify_tally) are inputs as well and must hold the caller's
+ *    values.  tests/test_gpu_output_contract.py holds the calls to this with dirty, guarded outputs.
  */
 #ifndef BTLBF_H
 #define BTLBF_H
@@ -244,7 +254,8 @@ int btlbf_contains_seqs(btlbf_filter* f, const char* seq, uint64_t len, const bt
 int btlbf_insert_and_check_seqs(btlbf_filter* f, const char* seq, uint64_t len,
                                 const btlbf_layout* layout, uint64_t* hit_bits, uint64_t* valid_bits,
                                 uint64_t* counts, int mem, void* stream);
-/* minCount per window (CountingBloomFilter.hpp:53-64): min_out[p], len bytes, 0 for unclean windows */
+/* minCount per window (CountingBloomFilter.hpp:53-64): min_out[p] is defined for all len bytes -- the minimum for a
+ * clean window, 0 for unclean windows and for the positions past a sequence's last window */
 int btlbf_min_count_seqs(btlbf_filter* f, const char* seq, uint64_t len, const btlbf_layout* layout,
                          uint8_t* min_out, uint64_t* valid_bits, int mem, void* stream);
 
@@ -272,7 +283,8 @@ int btlbf_min_count_hashes(btlbf_filter* f, const uint64_t* hashes, uint64_t n, 
 int btlbf_insert_kmers(btlbf_filter* f, const char* kmers, uint64_t n, int op, int order, int mem,
                        void* stream);
 int btlbf_contains_kmers(btlbf_filter* f, const char* kmers, uint64_t n, uint8_t* out, int mem, void* stream);
-/* the hash values alone: hashes[i*hash_num ..) and (optionally) valid[i] for k-mer i */
+/* the hash values alone: hashes[i*hash_num ..) and (optionally) valid[i] for k-mer i; a k-mer without a defined
+ * value has valid[i] = 0 and a row of zeros */
 int btlbf_hash_kmers(unsigned kmer_size, unsigned hash_num, const char* kmers, uint64_t n, uint64_t* hashes,
                      uint8_t* valid, int mem, int device, void* stream);
 
@@ -280,7 +292,8 @@ int btlbf_hash_kmers(unsigned kmer_size, unsigned hash_num, const char* kmers, u
  * ntHashIterator (vendor/ntHashIterator.hpp:38,93): hashes[p*h .. p*h+h) for window p (zeros when
  * not clean), valid_bits as above.  With seeds != NULL: stHashIterator(seq, seeds, n_seeds, h2, k)
  * (vendor/stHashIterator.hpp:53,94-103), h = n_seeds*h2 values per window and strand_bits[p] bit j =
- * strandArray()[j] (h <= 64 in that case).  Buffers live in `mem` space. */
+ * strandArray()[j] (h <= 64 in that case); strand_bits[p] is 0 for windows that are not clean, all len words
+ * are written.  Buffers live in `mem` space. */
 int btlbf_hash_seqs(unsigned kmer_size, unsigned hash_num, const char* const* seeds, unsigned n_seeds,
                     unsigned h2, const char* seq, uint64_t len, const btlbf_layout* layout,
                     uint64_t* hashes, uint64_t* valid_bits, uint64_t* strand_bits, int mem,
