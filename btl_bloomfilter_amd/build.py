@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 TAG = os.environ.get("BTLBF_BUILD_TAG", "")
 OBJ = os.path.join(HERE, "_build" + ("_" + TAG if TAG else ""))
 LIB = os.path.join(HERE, "libbtlbf%s.so" % ("_" + TAG if TAG else ""))
-HEADERS = ["internal.hpp", "mibf_plan.hpp", "mibf_zip.hpp", "mibf_classify_core.hpp", "host_internal.hpp", "host_partition.hpp", "device_utils.hpp", "seq_core.hpp", "partition_core.hpp",
+HEADERS = ["internal.hpp", "mibf_plan.hpp", "part_plan.hpp", "mibf_zip.hpp", "mibf_classify_core.hpp", "host_internal.hpp", "host_partition.hpp", "device_utils.hpp", "seq_core.hpp", "partition_core.hpp",
            os.path.join("..", "..", "include", "btlbf.h")]
 # host units (the C ABI over host_internal.hpp) and kernel units; tools/sanitize_host.sh reads both lists
 HOST_UNITS = ["capi", "host_io", "host_seq", "host_query", "host_partition", "host_aux", "host_mibf", "host_mibf_probs",

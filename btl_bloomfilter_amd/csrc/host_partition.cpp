@@ -7,14 +7,17 @@
 // the query routing (host_query.cpp) decides and executes with: that is declared in host_partition.hpp, which only
 // these two units include.  The sequence path (host_seq.cpp) enters through want_partitioned and partitioned_insert
 // (host_internal.hpp) and, for queries, through host_query.cpp's contains_routed.  The scratch lives in the filter's
-// DevScratch buffers.  Kernels: partition_kernels.hip, part_hash_inst.hip.
+// DevScratch buffers.  Kernels: partition_kernels.hip, part_hash_inst.hip.  How a call is cut into batches under the
+// scratch budget -- one batch, carried batches with one pass C, or independent batches -- is part_plan.hpp's arithmetic.
 #include "../../include/btlbf.h"
 #include "internal.hpp"
 #include "host_internal.hpp"
 #include "host_partition.hpp"
+#include "part_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -29,14 +32,8 @@ static constexpr uint64_t kFailTableSlots = 2 * kFailCap; // power of two
 // entries a FRESH insert batch (partitioned_insert) may report as explicit positions instead of staging them
 static constexpr uint64_t kFreshSpillCap = 16ull << 20;
 
-// chunks a region needs for `mean_entries` expected entries (Poisson: mean + 8 sigma) plus the
-// partially filled chunk flushed at kernel end
-// (chunks of `epc` entries: kChunk, or kPackChunk on a packed level)
-uint32_t chunks_for(double mean_entries, uint32_t tail_chunks, uint32_t epc = kChunk)
-{
-	const double m = mean_entries + 8.0 * std::sqrt(mean_entries + 1.0) + 32.0;
-	return (uint32_t)std::min<double>(4.0e9, std::ceil(m / (double)epc)) + tail_chunks;
-}
+// (chunks_for, tiles_for_caps, level_bytes: part_plan.hpp, the byte arithmetic of every plan made here)
+static_assert(kPlanChunkBytes == kChunk * 4, "part_plan.hpp counts chunks of kChunk words");
 
 unsigned ceil_log2(uint64_t x)
 {
@@ -142,6 +139,22 @@ bool packed_enabled()
 	return !(e && e[0] == '0');
 }
 
+// tuning knob: BTLBF_CARRY=0 keeps the independent batches where a call does not fit one (read at plan time)
+bool carry_enabled()
+{
+	const char* e = getenv("BTLBF_CARRY");
+	return !(e && e[0] == '0');
+}
+
+// BTLBF_CARRY_FORCE=K (1 .. kCarryMaxBatches) exists for tests: K equal carried batches even where one batch would fit,
+// so that small calls exercise the carried form
+uint32_t carry_forced()
+{
+	const char* e = getenv("BTLBF_CARRY_FORCE");
+	const int v = e ? atoi(e) : 0;
+	return v >= 1 && v <= (int)kCarryMaxBatches ? (uint32_t)v : 0;
+}
+
 // capacities + byte sizes for `entries` expected entries in the whole batch
 void plan_caps(PartPlan& pl, double entries, int first_level)
 {
@@ -155,15 +168,16 @@ void plan_caps(PartPlan& pl, double entries, int first_level)
 		// (part_packs); pass A's output, other split levels and counting filters keep 32-bit entries.
 		// BTLBF_PACKED=0 (tuning knob, read at plan time like BTLBF_SPLIT_BITS) keeps every level on 32-bit entries.
 		l.packed = j >= 1 && j == pl.n_levels - 1 && !pl.counting && part_packs(l.P, l.shift) && packed_enabled();
-		l.cap = chunks_for(entries / (useful * l.regions), 1, part_epc(l.packed));
 		l.alloc_bins = l.bins;
 		if (j >= 1 && pl.group_bins) {
 			l.alloc_bins = pl.group_bins;
 			for (int i = 1; i <= j; ++i)
 				l.alloc_bins *= pl.lv[i].P;
 		}
-		l.cnt_bytes = ((uint64_t)l.alloc_bins * l.regions * 4 + 255) / 256 * 256;
-		l.ent_bytes = (uint64_t)l.alloc_bins * l.regions * l.cap * (kChunk * 4);
+		const LevelBytes lb = level_bytes(entries, useful, l.alloc_bins, l.regions, part_epc(l.packed));
+		l.cap = lb.cap;
+		l.cnt_bytes = lb.cnt_bytes;
+		l.ent_bytes = lb.ent_bytes;
 		pl.bytes_total += l.cnt_bytes + l.ent_bytes;
 	}
 }
@@ -184,13 +198,6 @@ unsigned cu_count(int device)
 	int cus = 256;
 	(void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
 	return (unsigned)cus;
-}
-
-// pass A gives every workgroup (= region) ceil(tiles / regions) tiles: capacities are planned for the
-// fullest region, which matters when a batch has only a few tiles per workgroup
-uint64_t tiles_for_caps(uint64_t tiles, uint32_t regions)
-{
-	return regions ? (tiles + regions - 1) / regions * regions : tiles;
 }
 
 // expected probes of one full pass-A tile (+1 so that capacities never come out as zero)
@@ -223,8 +230,9 @@ PartSide part_side(const btlbf_filter* f, const PartPlan* pl = nullptr)
 // run the split levels lv[1..] over the level-0 data `in0`, then the apply / test pass
 // in0 holds level-0 bins [bin_offset, bin_offset + n_bins0) of the local array (bin i of in0 = absolute bin
 // bin_offset + i); the whole array by default
+// `carried`: the blocks earlier batches of the call left (run_unit), which pass C walks behind each group's own regions
 int run_levels(btlbf_filter* f, PartPlan& pl, PartIn in0, const PartSide& sd, int query, hipStream_t s,
-               uint32_t bin_offset = 0, uint32_t n_bins0 = 0)
+               uint32_t bin_offset = 0, uint32_t n_bins0 = 0, const PartIn* carried = nullptr)
 {
 	const int exact = sd.counting && !query; // counter increments: every entry exactly once
 	if (f->lazy_zero && !(sd.fresh && !query)) // only a fresh insert may run on a lazily cleared array
@@ -255,7 +263,48 @@ int run_levels(btlbf_filter* f, PartPlan& pl, PartIn in0, const PartSide& sd, in
 			break;
 		const uint64_t n_seg = std::min<uint64_t>(n_in, pl.n_seg - seg_first);
 		ProfSpan ps(f, prof_apply, s);
-		HIP_TRY(launch_part_apply(f->d_data, f->local_bytes, pl.seg_shift, seg_first, n_seg, in, sd, query, s));
+		HIP_TRY(launch_part_apply(f->d_data, f->local_bytes, pl.seg_shift, seg_first, n_seg, in, sd, query, s, f->part.p,
+		                          carried));
+	}
+	return BTLBF_OK;
+}
+
+// A UNIT of a call: the tiles that reach one pass C -- one of the independent batches, or under a carried plan the
+// whole call.
+struct PartUnit {
+	uint64_t first = 0, n = 0;
+};
+PartUnit part_unit(const PartPlan& pl, uint64_t total_tiles, uint64_t t0)
+{
+	if (pl.carry_k)
+		return PartUnit{0, total_tiles};
+	return PartUnit{t0, std::min<uint64_t>(pl.tiles_per_batch, total_tiles - t0)};
+}
+
+// The passes of a unit up to and including its pass C.  Carried plan: carried batch j is hashed and split, all level-0
+// bins at once, into block j of pl.carry (absolute segment numbers); the final batch runs group by group, its pass C
+// taking the blocks along.  `a`: the call's arguments with the outputs pass A writes; the tile range is set here.
+int run_unit(btlbf_filter* f, PartPlan& pl, SeqArgs a, const PartUnit& u, const PartSide& sd, int query, hipStream_t s)
+{
+	const int exact = sd.counting && !query;
+	const uint32_t k = pl.carry_k;
+	const PartIn carried = pl.carry_in();
+	for (uint32_t j = 0; j <= k; ++j) {
+		a.first_tile = u.first + j * pl.carry_tiles;
+		a.n_tiles = j < k ? pl.carry_tiles : u.n - k * pl.carry_tiles;
+		{
+			ProfSpan ps(f, query ? BTLBF_PROF_QUERY_HASH : BTLBF_PROF_INSERT_HASH, s);
+			HIP_TRY(launch_part_hash(a, pl.lv[0].out(), pl.lv[0].shift, sd, query, s));
+		}
+		if (j < k) {
+			if (f->lazy_zero && !(sd.fresh && !query))
+				return fail(BTLBF_EINVAL, "internal error: partition passes on a lazily cleared array");
+			ProfSpan ps(f, query ? BTLBF_PROF_QUERY_SPLIT : BTLBF_PROF_INSERT_SPLIT, s);
+			HIP_TRY(launch_part_split(f->d_data, pl.lv[0].in(), 0, 0, pl.lv[0].bins, pl.carry_out(j), pl.carry.shift,
+			                          pl.lv[0].shift, sd, query, exact, s));
+		} else if (int rc = run_levels(f, pl, pl.lv[0].in(), sd, query, s, 0, 0, k ? &carried : nullptr)) {
+			return rc;
+		}
 	}
 	return BTLBF_OK;
 }
@@ -405,27 +454,79 @@ PartPrep part_prepare(btlbf_filter* f, const SeqArgs& base, int mode, double aut
 	const uint64_t extra_bytes = ((pp.tail.bytes + 255) / 256) * 256 + late_bytes;
 	// a shard fed every rank's reads (ShardedBloomFilter's gather mode) keeps only its window's share
 	const double ppt = probes_per_tile(f, pp.tiling) * ((double)f->mod.shard_len / (double)f->mod.size);
-	uint64_t tiles = pp.tiling.n_tiles;
-	for (int iter = 0; iter < 64; ++iter) {
-		plan_caps(pl, (double)tiles_for_caps(tiles, l0.regions) * ppt, 0);
+	auto batch_bytes = [&](uint64_t t) {
+		plan_caps(pl, (double)tiles_for_caps(t, l0.regions) * ppt, 0);
 		pl.bytes_total += extra_bytes;
-		if (pl.bytes_total <= budget || tiles <= 1)
-			break;
-		const double ratio = (double)budget / (double)pl.bytes_total;
-		const uint64_t nt = (uint64_t)((double)tiles * ratio * 0.95);
-		tiles = nt >= tiles ? tiles - 1 : (nt ? nt : 1);
-	}
-	if (pl.bytes_total > budget)
+		return pl.bytes_total;
+	};
+	const uint64_t tiles = batch_tiles_for_budget(pp.tiling.n_tiles, budget, batch_bytes);
+	if (tiles == 0)
 		return pp;
+	batch_bytes(tiles);
+	// A call that does not fit one batch: carried batches and ONE pass C where a one-split plan allows it (part_plan.hpp);
+	// counting filters included -- their carried entries keep 32 bits and exact counts, and are read once.
+	// Plans with groups only: those are the filters whose sweep costs something (16 level-0 bins and more), and a call
+	// then still has more pass-C launches than pass-A launches.
+	const uint32_t forced = carry_enabled() ? carry_forced() : 0;
+	if ((tiles < pp.tiling.n_tiles || forced) && pl.n_levels == 2 && pl.group_bins && carry_enabled()) {
+		CarryGeom g;
+		g.n_tiles = pp.tiling.n_tiles;
+		g.probes_per_tile = ppt;
+		g.regions0 = l0.regions;
+		g.bins0 = l0.bins;
+		g.bins1 = pl.lv[1].bins;
+		g.useful1 = std::min<uint64_t>(pl.n_seg, pl.lv[1].bins);
+		g.group_bins1 = pl.lv[1].alloc_bins;
+		g.regions_group = pl.lv[1].regions;
+		g.regions_carry = split_slices(l0.bins, l0.regions, cu_count(f->device));
+		g.epc1 = part_epc(pl.lv[1].packed);
+		g.extra_bytes = extra_bytes;
+		const CarryPlan cp = forced ? plan_forced(g, budget, forced) : plan_call(g, budget);
+		if (cp.K) {
+			auto take = [](PartLevel& l, const LevelBytes& b) {
+				l.cap = b.cap;
+				l.cnt_bytes = b.cnt_bytes;
+				l.ent_bytes = b.ent_bytes;
+			};
+			take(l0, cp.l0);
+			take(pl.lv[1], cp.group);
+			pl.carry = pl.lv[1];
+			pl.carry.regions = g.regions_carry;
+			pl.carry.alloc_bins = pl.carry.bins;
+			pl.carry.cap = cp.block.cap;
+			pl.carry.cnt_bytes = cp.carry_cnt_bytes;
+			pl.carry.ent_bytes = cp.K * cp.block.ent_bytes;
+			pl.carry_k = cp.K;
+			pl.carry_tiles = cp.tiles_carried;
+			pl.bytes_total = cp.bytes_total;
+		}
+	}
 	// AUTO: a batch that the scratch budget has cut small is not worth a sweep of the array either (the rule
 	// want_partitioned applies to the whole call, applied to one batch): a filter that nearly fills the HBM
 	// leaves a few GB for scratch, and the direct kernels are then the faster path
-	if (mode == BTLBF_INSERT_AUTO && tiles < pp.tiling.n_tiles && (double)tiles * ppt < auto_ratio * (double)f->local_bytes)
+	// (a carried plan sweeps once for the whole call, which want_partitioned has weighed already)
+	if (mode == BTLBF_INSERT_AUTO && !pl.carry_k && tiles < pp.tiling.n_tiles &&
+	    (double)tiles * ppt < auto_ratio * (double)f->local_bytes)
 		return pp;
-	pl.tiles_per_batch = tiles;
+	pl.tiles_per_batch = pl.carry_k ? pp.tiling.n_tiles : tiles;
 	if (!f->part.grow(pl.bytes_total, f->device))
 		return pp; // no room for scratch: the caller falls back to the direct kernels
+	if (getenv("BTLBF_PLAN_LOG")) // diagnostic: the plan of every call, one line on stderr
+		fprintf(stderr,
+		        "btlbf plan: budget %llu tiles %llu carried batches %u of %llu tiles (independent batches of %llu) scratch %llu "
+		        "level0 %llu group %llu carried %llu caps %u %u %u\n",
+		        (unsigned long long)budget, (unsigned long long)pp.tiling.n_tiles, pl.carry_k, (unsigned long long)pl.carry_tiles,
+		        (unsigned long long)pl.tiles_per_batch, (unsigned long long)pl.bytes_total,
+		        (unsigned long long)(l0.cnt_bytes + l0.ent_bytes),
+		        (unsigned long long)(pl.n_levels >= 2 ? pl.lv[1].cnt_bytes + pl.lv[1].ent_bytes : 0),
+		        (unsigned long long)(pl.carry_k ? pl.carry.cnt_bytes + pl.carry.ent_bytes : 0), l0.cap,
+		        pl.n_levels >= 2 ? pl.lv[1].cap : 0, pl.carry_k ? pl.carry.cap : 0);
 	pp.extra = carve_levels(pl, static_cast<uint8_t*>(f->part.p), 0);
+	if (pl.carry_k) {
+		pl.carry.cnt = reinterpret_cast<uint32_t*>(pp.extra);
+		pl.carry.ent = reinterpret_cast<uint32_t*>(pp.extra + pl.carry.cnt_bytes);
+		pp.extra += pl.carry.cnt_bytes + pl.carry.ent_bytes;
+	}
 	pl.late_buf = pl.late_cap ? reinterpret_cast<uint32_t*>(pp.extra + ((pp.tail.bytes + 255) / 256) * 256) : nullptr;
 	pp.ok = true;
 	return pp;
@@ -492,7 +593,7 @@ int route_plan(const btlbf_filter* f, uint64_t len, const LayoutParams& lay, uns
 	rp.regions = cu_count(f->device);
 	const PartTiling tl = part_tiling(f->hp, rp.bins, lay, len);
 	const double entries = (double)tiles_for_caps(tl.n_tiles, rp.regions) * probes_per_tile(f, tl) / rp.n_windows;
-	rp.cap = chunks_for(entries / ((double)rp.bins * rp.regions), 1);
+	rp.cap = chunks_for(entries / ((double)rp.bins * rp.regions), 1, kChunk);
 	rp.ent_bytes_per_shard = (uint64_t)rp.bins_per_shard * rp.regions * rp.cap * (kChunk * 4);
 	rp.cnt_bytes_per_shard = (uint64_t)rp.bins_per_shard * rp.regions * 4;
 	return BTLBF_OK;
@@ -607,10 +708,9 @@ int partitioned_insert(btlbf_filter* f, const SeqArgs& base, hipStream_t s, bool
 		return BTLBF_OK;
 	PartPlan& pl = pp.pl;
 	const uint64_t total_tiles = pp.tiling.n_tiles;
+	// unit by unit (part_unit): under a carried plan the fresh state, the spill list and the retry belong to the call
 	for (uint64_t t0 = 0; t0 < total_tiles; t0 += pl.tiles_per_batch) {
-		SeqArgs a = base;
-		a.first_tile = t0;
-		a.n_tiles = std::min<uint64_t>(pl.tiles_per_batch, total_tiles - t0);
+		const PartUnit u = part_unit(pl, total_tiles, t0);
 		for (int attempt = 0; attempt < 2; ++attempt) {
 			const bool fresh = f->lazy_zero;
 			PartSide sd = part_side(f, &pl);
@@ -622,11 +722,7 @@ int partitioned_insert(btlbf_filter* f, const SeqArgs& base, hipStream_t s, bool
 				sd.spill_cap = pp.tail.spill_cap;
 				HIP_TRY(hipMemsetAsync(sd.spill_count, 0, 8, s));
 			}
-			{
-				ProfSpan ps(f, BTLBF_PROF_INSERT_HASH, s);
-				HIP_TRY(launch_part_hash(a, pl.lv[0].out(), pl.lv[0].shift, sd, 0, s));
-			}
-			if (int rc = run_levels(f, pl, pl.lv[0].in(), sd, 0, s))
+			if (int rc = run_unit(f, pl, base, u, sd, 0, s))
 				return rc;
 			if (!fresh)
 				break;
@@ -679,28 +775,25 @@ int part_query(btlbf_filter* f, const SeqArgs& base, uint8_t* hit_bits, uint8_t*
 		HIP_TRY(hipMemsetAsync(counts, 0, 16, s));
 	const uint64_t seq_tw = (uint64_t)seq_tile_windows();
 	const uint64_t seq_tiles_all = (base.len + seq_tw - 1) / seq_tw;
+	// unit by unit (part_unit): under a carried plan the fail list is the call's, and one resolve step follows its
+	// single test pass
 	for (uint64_t t0 = 0; t0 < total_tiles; t0 += pl.tiles_per_batch) {
+		const PartUnit u = part_unit(pl, total_tiles, t0);
 		SeqArgs a = base;
-		a.first_tile = t0;
-		a.n_tiles = std::min<uint64_t>(pl.tiles_per_batch, total_tiles - t0);
 		a.hit_bits = hit_bits;
 		a.valid_bits = valid_bits;
 		a.counts = counts; // pass A adds the clean-window count to counts[0]
 		HIP_TRY(hipMemsetAsync(sd.fail_count, 0, 8, s));
-		{
-			ProfSpan ps(f, BTLBF_PROF_QUERY_HASH, s);
-			HIP_TRY(launch_part_hash(a, pl.lv[0].out(), pl.lv[0].shift, sd, 1, s));
-		}
-		if (int rc = run_levels(f, pl, pl.lv[0].in(), sd, 1, s))
+		if (int rc = run_unit(f, pl, a, u, sd, 1, s))
 			return rc;
-		// redo / refine this batch's window range with the direct kernels: their tiles that overlap the
-		// batch's bytes.  A tile more at either end is harmless: a failed position is a bit that IS clear,
+		// redo / refine this unit's window range with the direct kernels: their tiles that overlap the
+		// unit's bytes.  A tile more at either end is harmless: a failed position is a bit that IS clear,
 		// so clearing any window that owns it is right, and a direct redo computes the true answer.
 		// What happens is decided on the device (GATE_*): no failed position -> nothing; up to fail_cap -> they become
 		// a hash set and one hashing pass clears the windows that own one; more -> the range is redone by the direct
 		// kernel.  All launches are issued, the ones decided against return at once: no host round trip per batch.
-		const uint64_t first = t0 * pp.tiling.tile_bytes / seq_tw;
-		const uint64_t end_b = std::min<uint64_t>(base.len, (t0 + a.n_tiles) * (uint64_t)pp.tiling.tile_bytes);
+		const uint64_t first = u.first * pp.tiling.tile_bytes / seq_tw;
+		const uint64_t end_b = std::min<uint64_t>(base.len, (u.first + u.n) * (uint64_t)pp.tiling.tile_bytes);
 		const uint64_t n = std::min<uint64_t>((end_b + seq_tw - 1) / seq_tw, seq_tiles_all) - first;
 		ProfSpan ps(f, BTLBF_PROF_QUERY_RESOLVE, s);
 		HIP_TRY(launch_failset_auto(sd.fail_list, sd.fail_count, pp.tail.fail_cap, table, pp.tail.table_slots, ctl, s));

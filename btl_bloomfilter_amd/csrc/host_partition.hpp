@@ -45,6 +45,19 @@ struct PartPlan {
 	// round parity (part_hash_inst.hip): [regions][2][late_cap] words behind the tail of the scratch
 	uint32_t* late_buf = nullptr;
 	uint32_t late_cap = 0;
+	// A CARRIED plan (part_plan.hpp; carry_k != 0, one-split plans only): the call runs carry_k carried batches of
+	// carry_tiles tiles and a final batch of the rest.  `carry` is lv[1] in its ungrouped form -- every bin of the array,
+	// absolute segment numbers --, its arrays holding the carry_k blocks one after the other ([block][bin][region]).
+	uint32_t carry_k = 0;
+	uint64_t carry_tiles = 0;
+	PartLevel carry;
+	PartOut carry_out(uint32_t j) const
+	{
+		const uint64_t regs = (uint64_t)carry.bins * carry.regions;
+		return PartOut{carry.P, carry.regions, carry.cap, carry.packed, carry.cnt + j * regs,
+		               carry.ent + j * regs * carry.cap * kChunk};
+	}
+	PartIn carry_in() const { return PartIn{carry_k, carry.bins, carry.regions, carry.cap, carry.cnt, carry.ent, carry.packed}; }
 	// level-0 bins that are split and applied together, of the n_bins0 a pass has (plans without groups: all of them)
 	uint32_t group(uint32_t n_bins0) const { return n_levels >= 2 && group_bins ? group_bins : n_bins0; }
 };

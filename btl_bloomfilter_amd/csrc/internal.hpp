@@ -253,8 +253,11 @@ hipError_t launch_part_split(void* filter, const PartIn& in, uint32_t first_in, 
                              const PartOut& out, uint32_t sub_shift, uint32_t in_shift, const PartSide& sd, int query,
                              int exact, hipStream_t s);
 // seg_shift = log2(positions per segment); the array holds bits, or uint8_t counters when sd.counting
+// `carried`: a second input under absolute segment numbers (the carried blocks of a call), which
+// lies with `in` in the scratch that starts at `arena`
 hipError_t launch_part_apply(void* filter, uint64_t local_bytes, uint32_t seg_shift, uint64_t seg_first, uint64_t n_seg,
-                             const PartIn& in, const PartSide& sd, int query, hipStream_t s);
+                             const PartIn& in, const PartSide& sd, int query, hipStream_t s, const void* arena = nullptr,
+                             const PartIn* carried = nullptr);
 hipError_t launch_failset_build(const uint64_t* fail_list, uint64_t n, uint64_t* table, uint64_t mask, hipStream_t s);
 // the same decided on the device from the fail count of a batch: ctl[0] := table mask, ctl[1] := mode | n << 32 with
 // mode 0 = no failed position (nothing to do), 1 = table built (resolve), 2 = more than fail_cap (redo directly)

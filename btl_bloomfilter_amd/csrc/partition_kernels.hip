@@ -27,6 +27,7 @@
 // 1024-way split to entries of at most 20 bits): three entries per 64-bit word, 48 per line; its rings hold the packed
 // words themselves (partition_core.hpp part_pack_or), and pass C takes a 16-byte vector as six entries.
 #include "partition_core.hpp"
+#include "part_plan.hpp"
 #include <algorithm>
 
 namespace btlbf {
@@ -163,6 +164,8 @@ __global__ __launch_bounds__(kPartThreads) void part_split_kernel(void* filter, 
 // Input bin blockIdx.x holds the entries of segment seg_first + blockIdx.x (group-relative numbering).
 static constexpr uint32_t kApplyMaxRegions = 1024; // region table kept in LDS (more: plain loop)
 static constexpr uint32_t kApplyFewRegions = 16;    // up to here the regions are walked one by one (uniform control flow)
+static_assert(kApplyFewRegions == kCarryMaxRegions && kApplyMaxRegions == kCarryMaxTabled,
+              "a carried plan keeps pass C on the walk the group buffer alone puts it on (part_plan.hpp)");
 
 // what pass C does with an entry (= position inside the segment held in LDS)
 enum ApplyMode : int {
@@ -243,10 +246,15 @@ __device__ __forceinline__ void apply_vec(uint32_t* lds, const uint4& q, uint32_
 // NT = 512 for 64 KiB segments (two workgroups per CU), 1024 for 128 KiB segments (one per CU).
 // Every region is read up to its exact entry count (its last vector may be padded).
 // PK: the input holds packed chunks (in.packed): kPackChunk entries per chunk, six per vector.
+// CARRIED input (cin.blocks != 0): the regions earlier batches of the call left for this segment,
+// one per block and writer, under the segment's ABSOLUTE number; same format as `in`, a capacity of their own.  They
+// follow the regions of `in` in the walk.  Both inputs lie in one arena, and the region table keeps where a region
+// starts as a 32-bit count of chunks from `arena` (without a carried input: arena == in.ent).
 template <int MODE, int NT, bool PK>
 __global__ __launch_bounds__(NT) void part_apply_kernel(uint8_t* filter, uint64_t local_bytes,
                                                         uint32_t seg_shift, uint32_t seg_first,
-                                                        const PartIn in, const PartSide sd)
+                                                        const PartIn in, const PartSide sd,
+                                                        const uint32_t* arena, const PartIn cin)
 {
 	constexpr bool QUERY = (MODE & 1) != 0;
 	constexpr bool kNtEnt = !QUERY; // streaming entry loads pay for the passes that write the segment back (see nt_load4)
@@ -254,28 +262,37 @@ __global__ __launch_bounds__(NT) void part_apply_kernel(uint8_t* filter, uint64_
 	extern __shared__ __attribute__((aligned(16))) uint8_t dyn[];
 	__shared__ uint32_t any;
 	__shared__ uint32_t r_n[kApplyMaxRegions];   // entries in region r of this bin
-	__shared__ uint32_t r_reg[kApplyMaxRegions]; // its index into in.cnt / in.ent
+	__shared__ uint32_t r_base[kApplyMaxRegions]; // where it starts: chunks from `arena`
 	const uint32_t tid = threadIdx.x;
 	const uint32_t ibin = blockIdx.x;
 	const uint32_t seg = seg_first + blockIdx.x;
-	const uint32_t n_regions = in.blocks * in.regions_per_block;
+	const uint32_t n_cur = in.blocks * in.regions_per_block;
+	const uint32_t n_regions = n_cur + cin.blocks * cin.regions_per_block;
 	constexpr uint32_t kVecE = PK ? 6 : 4;                // entries per 16-byte vector
-	const uint32_t cap_entries = in.cap * (PK ? kPackChunk : kChunk);
-	const uint32_t cap_words = in.cap * kChunk;           // a region in uint32 words, whatever it holds
+	constexpr uint32_t kEpc = PK ? kPackChunk : kChunk;   // entries per chunk
+	const uint32_t cur0 = (uint32_t)((in.ent - arena) >> kChunkShift), car0 = (uint32_t)((cin.ent - arena) >> kChunkShift);
 	const bool tabled = n_regions <= kApplyMaxRegions;
+	// region r of this segment: its entries and its first chunk
+	auto region_at = [&](uint32_t r, uint32_t& n, uint32_t& base) {
+		const bool cur = r < n_cur;
+		const uint32_t reg = cur ? part_in_region(in, ibin, r) : part_in_region(cin, seg, r - n_cur);
+		const uint32_t cap = cur ? in.cap : cin.cap;
+		n = cur ? in.cnt[reg] : cin.cnt[reg];
+		if (n > cap * kEpc)
+			n = cap * kEpc;
+		base = (cur ? cur0 : car0) + reg * cap;
+	};
 	if (tid == 0)
 		any = 0;
 	__syncthreads();
 	uint32_t mine = 0;
 	for (uint32_t r = tid; r < n_regions; r += NT) {
-		const uint32_t reg = part_in_region(in, ibin, r);
-		uint32_t n = in.cnt[reg];
-		if (n > cap_entries)
-			n = cap_entries;
+		uint32_t n, cb;
+		region_at(r, n, cb);
 		mine |= n;
 		if (tabled) {
 			r_n[r] = n;
-			r_reg[r] = reg;
+			r_base[r] = cb;
 		}
 	}
 	if (mine)
@@ -311,7 +328,7 @@ __global__ __launch_bounds__(NT) void part_apply_kernel(uint8_t* filter, uint64_
 		dst = make_uint4(0, 0, 0, 0);                                                                          \
 		if (wr[u] < n_regions) {                                                                               \
 			lft = r_n[wr[u]] - wi[u] * kVecE;                                                                  \
-			dst = reinterpret_cast<const uint4*>(in.ent + (uint64_t)r_reg[wr[u]] * cap_words)[wi[u]];          \
+			dst = reinterpret_cast<const uint4*>(arena + (uint64_t)r_base[wr[u]] * kChunk)[wi[u]];             \
 		}                                                                                                      \
 	} while (0)
 	// FEW regions (the usual case behind a split pass: one region per slice): they are walked one after the
@@ -337,12 +354,12 @@ __global__ __launch_bounds__(NT) void part_apply_kernel(uint8_t* filter, uint64_
 	};
 	auto few_request = [&](uint4 (&d)[kFewU], uint32_t (&lf)[kFewU]) {
 		const uint32_t n0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)r_n[f_r]), nv0 = (n0 + kVecE - 1) / kVecE;
-		const uint32_t reg0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)r_reg[f_r]);
+		const uint32_t reg0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)r_base[f_r]);
 		const bool two = f_r + 1 < n_regions;
 		const uint32_t n1 = two ? (uint32_t)__builtin_amdgcn_readfirstlane((int)r_n[two ? f_r + 1 : f_r]) : 0u, nv1 = (n1 + kVecE - 1) / kVecE;
-		const uint32_t reg1 = two ? (uint32_t)__builtin_amdgcn_readfirstlane((int)r_reg[two ? f_r + 1 : f_r]) : reg0;
-		const uint4* src0 = reinterpret_cast<const uint4*>(in.ent + (uint64_t)reg0 * cap_words);
-		const uint4* src1 = reinterpret_cast<const uint4*>(in.ent + (uint64_t)reg1 * cap_words);
+		const uint32_t reg1 = two ? (uint32_t)__builtin_amdgcn_readfirstlane((int)r_base[two ? f_r + 1 : f_r]) : reg0;
+		const uint4* src0 = reinterpret_cast<const uint4*>(arena + (uint64_t)reg0 * kChunk);
+		const uint4* src1 = reinterpret_cast<const uint4*>(arena + (uint64_t)reg1 * kChunk);
 #pragma unroll
 		for (int u = 0; u < kFewU; ++u) {
 			const uint32_t v = f_off + (uint32_t)u * NT + tid; // vector index counted from the start of region f_r
@@ -440,11 +457,9 @@ __global__ __launch_bounds__(NT) void part_apply_kernel(uint8_t* filter, uint64_
 #undef BTLBF_FETCH
 	} else {
 		for (uint32_t r = 0; r < n_regions; ++r) {
-			const uint32_t reg = part_in_region(in, ibin, r);
-			uint32_t n = in.cnt[reg];
-			if (n > cap_entries)
-				n = cap_entries;
-			const uint32_t* e1 = in.ent + (uint64_t)reg * cap_words;
+			uint32_t n, cb;
+			region_at(r, n, cb);
+			const uint32_t* e1 = arena + (uint64_t)cb * kChunk;
 			if (PK) { // word by word: the fields behind the last entry repeat it (bit filters only)
 				for (uint32_t i = tid; i < (n + 2) / 3; i += NT) {
 					uint32_t e3[3];
@@ -663,18 +678,35 @@ static auto apply_kernel(int mode, bool packed) -> decltype(&part_apply_kernel<A
 }
 
 hipError_t launch_part_apply(void* filter, uint64_t local_bytes, uint32_t seg_shift, uint64_t seg_first, uint64_t n_seg,
-                             const PartIn& in, const PartSide& sd, int query, hipStream_t s)
+                             const PartIn& in, const PartSide& sd, int query, hipStream_t s, const void* arena,
+                             const PartIn* carried)
 {
 	if (n_seg == 0)
 		return hipSuccess;
 	if (in.packed && (sd.counting || seg_shift > kPackBits))
 		return hipErrorInvalidValue;
+	PartIn cin{};
+	const uint32_t* base = in.ent;
+	if (carried && carried->blocks) {
+		// both inputs in one arena, at whole chunks of it, in one format; the carried blocks cover the segments asked for
+		cin = *carried;
+		base = static_cast<const uint32_t*>(arena);
+		const uint64_t chunk_b = kChunk * 4, off_in = (const uint8_t*)in.ent - (const uint8_t*)base,
+		               off_c = (const uint8_t*)cin.ent - (const uint8_t*)base;
+		if (!base || in.ent < base || cin.ent < base || off_in % chunk_b || off_c % chunk_b || cin.packed != in.packed ||
+		    seg_first + n_seg > cin.bins_per_block || cin.regions_per_block == 0)
+			return hipErrorInvalidValue;
+		const uint64_t end_in = off_in / chunk_b + (uint64_t)in.blocks * in.bins_per_block * in.regions_per_block * in.cap;
+		const uint64_t end_c = off_c / chunk_b + (uint64_t)cin.blocks * cin.bins_per_block * cin.regions_per_block * cin.cap;
+		if (std::max(end_in, end_c) > 0xffffffffull)
+			return hipErrorInvalidValue;
+	}
 	const int mode = (sd.counting ? APPLY_CNT_INC : APPLY_BIT_OR) + (query ? 1 : 0);
 	const size_t dyn = (size_t)1 << (seg_shift - (sd.counting ? 0 : 3)); // bytes of one segment
 	const bool wide = dyn > 64 * 1024; // 128 KiB segments: one workgroup of 1024 threads per CU
 	return part_launch(wide ? apply_kernel<1024>(mode, in.packed) : apply_kernel<512>(mode, in.packed), dim3((unsigned)n_seg),
 	                   dim3(wide ? 1024 : 512), dyn, s, static_cast<uint8_t*>(filter), local_bytes, seg_shift, (uint32_t)seg_first,
-	                   in, sd);
+	                   in, sd, base, cin);
 }
 
 // ---- failed-position set (partitioned query, resolve step) ----------------------------------------
