@@ -10,7 +10,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BTLBF_LIB") or os.path.join(HERE, "libbtlbf.so")
 
 HOST, DEVICE = 0, 1
-BLOOM, COUNTING8 = 0, 1
+BLOOM, COUNTING8, COUNTING16, COUNTING32, COUNTING64 = 0, 1, 2, 3, 4
+# counting kind of a counter width in bits, and back (btlbf_counter_bytes)
+COUNTING_KIND = {8: COUNTING8, 16: COUNTING16, 32: COUNTING32, 64: COUNTING64}
 INCREMENT_MIN, INCREMENT_ALL = 0, 1
 ORDER_PARALLEL, ORDER_SERIAL = 0, 1
 OK, EINVAL, ENOMEM, EIO, EFORMAT, EHIP = range(6)
@@ -64,6 +66,7 @@ _PROTOS = {
     "btlbf_header": (C.c_int, [_P, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "btlbf_store_shard": (C.c_int, [_P, C.c_char_p]),
     "btlbf_kind": (C.c_int, [_P]),
+    "btlbf_counter_bytes": (C.c_uint, [_P]),
     "btlbf_size": (C.c_uint64, [_P]),
     "btlbf_size_bytes": (C.c_uint64, [_P]),
     "btlbf_local_bytes": (C.c_uint64, [_P]),
@@ -132,6 +135,8 @@ _PROTOS = {
     "btlbf_contains_seqs": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(Layout), _P, _P, _P, C.c_int, _P]),
     "btlbf_insert_and_check_seqs": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(Layout), _P, _P, _P, C.c_int, _P]),
     "btlbf_min_count_seqs": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(Layout), _P, _P, C.c_int, _P]),
+    "btlbf_min_count_seqs_wide": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(Layout), _P, _P, C.c_int, _P]),
+    "btlbf_min_count_hashes_wide": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_int, _P]),
     "btlbf_insert_hashes": (C.c_int, [_P, _P, C.c_uint64, C.c_int, C.c_int, C.c_int, _P]),
     "btlbf_contains_hashes": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_int, _P]),
     "btlbf_insert_and_check_hashes": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_int, C.c_int, _P]),

@@ -278,13 +278,16 @@ int make_filter(btlbf_filter** out, int kind, uint64_t size, uint64_t size_bytes
 	if (!out)
 		return fail(BTLBF_EINVAL, "null out pointer");
 	*out = nullptr;
-	if (kind != BTLBF_BLOOM && kind != BTLBF_COUNTING8)
+	const int cb = kind_counter_bytes(kind);
+	if (cb < 0)
 		return fail(BTLBF_EINVAL, "unknown filter kind %d", kind);
+	if (cb > 1 && shard_count != 1)
+		return refuse_wide("a shard of a wide counting filter");
 	if (h == 0)
 		return fail(BTLBF_EINVAL, "hash_num must be >= 1");
 	if (k == 0 || k > 32768)
 		return fail(BTLBF_EINVAL, "kmer_size must be in 1..32768");
-	if (size < 8)
+	if (cb > 1 ? size < 1 : size < 8) // (8 bytes of wide counters are 4, 2 or 1 of them)
 		return fail(BTLBF_EINVAL, "filter size %llu too small", (unsigned long long)size);
 	if (shard_count == 0 || shard_index >= shard_count || size % shard_count ||
 	    (shard_count > 1 && (size / shard_count) % 64))
@@ -313,16 +316,17 @@ int make_filter(btlbf_filter** out, int kind, uint64_t size, uint64_t size_bytes
 	f->alloc_bytes = (f->local_bytes + 15) / 16 * 16;
 	fill_mod(f->mod, size, (uint64_t)shard_index * len, len);
 	fill_hash_params(f->hp, k, h);
+	// (a wide counting filter has the direct path only: "partitioned" in the environment is not for it)
 	if (const char* m = getenv("BTLBF_INSERT_MODE")) {
 		if (!strcmp(m, "direct"))
 			f->insert_mode = BTLBF_INSERT_DIRECT;
-		else if (!strcmp(m, "partitioned"))
+		else if (!strcmp(m, "partitioned") && cb <= 1)
 			f->insert_mode = BTLBF_INSERT_PARTITIONED;
 	}
 	if (const char* m = getenv("BTLBF_QUERY_MODE")) {
 		if (!strcmp(m, "direct"))
 			f->query_mode = BTLBF_INSERT_DIRECT;
-		else if (!strcmp(m, "partitioned"))
+		else if (!strcmp(m, "partitioned") && cb <= 1)
 			f->query_mode = BTLBF_INSERT_PARTITIONED;
 	}
 	hipError_t e = hipMalloc(&f->d_data, f->alloc_bytes);
@@ -416,6 +420,9 @@ extern "C" int btlbf_create(btlbf_filter** out, int kind, uint64_t size, unsigne
 		return make_filter(out, kind, size, size / 8, 0, 1, hash_num, kmer_size, 0, device);
 	}
 	const uint64_t bytes = cbf_round_bytes(size);
+	if (kind_counter_bytes(kind) > 1) // m_size = m_sizeInBytes / sizeof(T) counters (CountingBloomFilter.hpp:40-49)
+		return make_filter(out, kind, bytes / (uint64_t)kind_counter_bytes(kind), bytes, 0, 1, hash_num, kmer_size,
+		                   threshold, device);
 	return make_filter(out, kind, bytes, bytes, 0, 1, hash_num, kmer_size, threshold, device);
 }
 
@@ -429,6 +436,11 @@ extern "C" int btlbf_create_shard(btlbf_filter** out, int kind, uint64_t global_
 			            (unsigned long long)global_size);
 		return make_filter(out, kind, global_size, global_size / 8, shard_index, shard_count, hash_num,
 		                   kmer_size, 0, device);
+	}
+	if (kind_counter_bytes(kind) > 1) {
+		if (out)
+			*out = nullptr;
+		return refuse_wide("btlbf_create_shard");
 	}
 	const uint64_t bytes = cbf_round_bytes(global_size);
 	return make_filter(out, kind, bytes, bytes, shard_index, shard_count, hash_num, kmer_size, threshold,
@@ -460,6 +472,8 @@ extern "C" int btlbf_set_insert_mode(btlbf_filter* f, int mode, uint64_t scratch
 	FilterLock lk__(f);
 	if (!f || mode < BTLBF_INSERT_AUTO || mode > BTLBF_INSERT_PARTITIONED)
 		return fail(BTLBF_EINVAL, "bad insert mode");
+	if (is_wide(f) && mode == BTLBF_INSERT_PARTITIONED)
+		return refuse_wide("btlbf_set_insert_mode(PARTITIONED)");
 	f->insert_mode = mode;
 	f->part_budget = scratch_bytes;
 	return BTLBF_OK;
@@ -519,6 +533,8 @@ extern "C" int btlbf_set_query_mode(btlbf_filter* f, int mode)
 	FilterLock lk__(f);
 	if (!f || mode < BTLBF_INSERT_AUTO || mode > BTLBF_INSERT_PARTITIONED)
 		return fail(BTLBF_EINVAL, "bad query mode");
+	if (is_wide(f) && mode == BTLBF_INSERT_PARTITIONED)
+		return refuse_wide("btlbf_set_query_mode(PARTITIONED)");
 	f->query_mode = mode;
 	return BTLBF_OK;
 }
@@ -555,6 +571,7 @@ extern "C" int btlbf_set_spaced_seeds(btlbf_filter* f, const char* const* seeds,
 // attributes
 // -------------------------------------------------------------------------------------------------
 extern "C" int btlbf_kind(const btlbf_filter* f) { return f->kind; }
+extern "C" unsigned btlbf_counter_bytes(const btlbf_filter* f) { return counter_bytes(f); }
 extern "C" uint64_t btlbf_size(const btlbf_filter* f) { return f->size; }
 extern "C" uint64_t btlbf_size_bytes(const btlbf_filter* f) { return f->size_bytes; }
 extern "C" uint64_t btlbf_local_bytes(const btlbf_filter* f) { return f->local_bytes; }

@@ -21,11 +21,15 @@ static int popcount_mode(btlbf_filter* f, int mode, uint64_t* out)
 	MATERIALIZE(f, nullptr);
 	HIP_TRY(hipDeviceSynchronize()); // DEVICE-mode calls may have run on non-blocking user streams
 	HIP_TRY(hipMemset(f->d_scalar, 0, 8));
-	HIP_TRY(launch_popcount(f->d_data, f->alloc_bytes, mode, f->thr, f->d_scalar, nullptr));
+	const unsigned cb = is_wide(f) ? counter_bytes(f) : 1;
+	if (cb > 1)
+		HIP_TRY(launch_wide_popcount(f->d_data, f->alloc_bytes, (int)cb, mode, f->thr, f->d_scalar, nullptr));
+	else
+		HIP_TRY(launch_popcount(f->d_data, f->alloc_bytes, mode, f->thr, f->d_scalar, nullptr));
 	unsigned long long v = 0;
 	HIP_TRY(hipMemcpy(&v, f->d_scalar, 8, hipMemcpyDeviceToHost));
 	if (mode == 2 && f->thr == 0)
-		v -= f->alloc_bytes - f->local_bytes; // zero padding also passes ">= 0"
+		v -= (f->alloc_bytes - f->local_bytes) / cb; // zero padding also passes ">= 0"
 	*out = v;
 	return BTLBF_OK;
 }
@@ -33,13 +37,13 @@ static int popcount_mode(btlbf_filter* f, int mode, uint64_t* out)
 extern "C" int btlbf_popcount(btlbf_filter* f, uint64_t* out)
 {
 	FilterLock lk__(f);
-	return popcount_mode(f, f && f->kind == BTLBF_COUNTING8 ? 1 : 0, out);
+	return popcount_mode(f, f && is_counting(f) ? 1 : 0, out);
 }
 
 extern "C" int btlbf_filtered_popcount(btlbf_filter* f, uint64_t* out)
 {
 	FilterLock lk__(f);
-	if (f && f->kind != BTLBF_COUNTING8)
+	if (f && !is_counting(f))
 		return fail(BTLBF_EINVAL, "filtered_popcount needs a counting filter");
 	return popcount_mode(f, 2, out);
 }
@@ -50,7 +54,7 @@ extern "C" int btlbf_digest(btlbf_filter* f, uint64_t* out2)
 	if (!f || !out2)
 		return fail(BTLBF_EINVAL, "null argument");
 	// the first local position must start a 64-bit word of the whole array (shards are cut at multiples of 64)
-	const uint64_t per_word = f->kind == BTLBF_BLOOM ? 64 : 8;
+	const uint64_t per_word = is_counting(f) ? 8 / counter_bytes(f) : 64;
 	if (f->mod.shard_lo % per_word)
 		return fail(BTLBF_EINVAL, "digest: the shard does not start on a 64-bit word of the filter");
 	DeviceGuard g(f->device);
@@ -77,8 +81,12 @@ extern "C" int btlbf_compare(btlbf_filter* a, btlbf_filter* b, uint64_t* out3)
 	DevBuf acc;
 	HIP_TRY(acc.alloc(24));
 	HIP_TRY(hipMemset(acc.p, 0, 24));
-	HIP_TRY(launch_compare(a->d_data, b->d_data, a->alloc_bytes, a->kind == BTLBF_COUNTING8,
-	                       acc.as<unsigned long long>(), nullptr));
+	if (is_wide(a))
+		HIP_TRY(launch_wide_compare(a->d_data, b->d_data, a->alloc_bytes, (int)counter_bytes(a),
+		                            acc.as<unsigned long long>(), nullptr));
+	else
+		HIP_TRY(launch_compare(a->d_data, b->d_data, a->alloc_bytes, a->kind == BTLBF_COUNTING8,
+		                       acc.as<unsigned long long>(), nullptr));
 	unsigned long long v[3] = {0, 0, 0};
 	HIP_TRY(hipMemcpy(v, acc.p, 24, hipMemcpyDeviceToHost));
 	out3[0] = v[0];
@@ -210,6 +218,8 @@ extern "C" int btlbf_positions_seqs(btlbf_filter* f, const char* seq, uint64_t l
                                     uint64_t* valid_bits, void* stream)
 {
 	FilterLock lk__(f);
+	if (f && is_wide(f))
+		return refuse_wide("btlbf_positions_seqs");
 	int rc = seq_precheck(f);
 	if (rc)
 		return rc;
@@ -239,6 +249,8 @@ extern "C" int btlbf_positions_seqs(btlbf_filter* f, const char* seq, uint64_t l
 extern "C" int btlbf_insert_positions(btlbf_filter* f, const uint64_t* local_pos, uint64_t n, void* stream)
 {
 	FilterLock lk__(f);
+	if (f && is_wide(f))
+		return refuse_wide("btlbf_insert_positions");
 	if (!f || (n && !local_pos))
 		return fail(BTLBF_EINVAL, "null argument");
 	if (f->kind != BTLBF_BLOOM)
@@ -253,6 +265,8 @@ extern "C" int btlbf_test_positions(btlbf_filter* f, const uint64_t* local_pos, 
                                     void* stream)
 {
 	FilterLock lk__(f);
+	if (f && is_wide(f))
+		return refuse_wide("btlbf_test_positions");
 	if (!f || (n && (!local_pos || !out)))
 		return fail(BTLBF_EINVAL, "null argument");
 	if (f->kind != BTLBF_BLOOM)
@@ -364,6 +378,8 @@ extern "C" int btlbf_microbench(btlbf_filter* f, int kind, uint64_t n_access, ui
                                 double* seconds)
 {
 	FilterLock lk__(f);
+	if (f && is_wide(f))
+		return refuse_wide("btlbf_microbench");
 	if (!f || !seconds || !n_done)
 		return fail(BTLBF_EINVAL, "null argument");
 	{

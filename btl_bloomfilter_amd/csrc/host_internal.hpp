@@ -117,6 +117,30 @@ struct btlbf_filter {
 
 namespace btlbf {
 
+// The kinds: a bit filter, or counters of 1, 2, 4 or 8 bytes (CountingBloomFilter<T>).  Bytes per counter of a kind:
+// 0 for BTLBF_BLOOM, -1 for a kind there is none of.  The wide kinds (more than a byte) take the direct path only -- one
+// fused launch per call on the whole filter (wide_counter_kernels.hip): no shards, no partitioned pipeline, no routing.
+inline int kind_counter_bytes(int kind)
+{
+	switch (kind) {
+	case BTLBF_BLOOM: return 0;
+	case BTLBF_COUNTING8: return 1;
+	case BTLBF_COUNTING16: return 2;
+	case BTLBF_COUNTING32: return 4;
+	case BTLBF_COUNTING64: return 8;
+	default: return -1;
+	}
+}
+inline unsigned counter_bytes(const btlbf_filter* f) { return (unsigned)kind_counter_bytes(f->kind); }
+inline bool is_counting(const btlbf_filter* f) { return counter_bytes(f) != 0; }
+inline bool is_wide(const btlbf_filter* f) { return counter_bytes(f) > 1; }
+// what an entry point that a wide filter cannot take answers, before any HIP call: sets the message, returns EINVAL
+inline int refuse_wide(const char* what)
+{
+	return btlbf_set_error(BTLBF_EINVAL, "%s: counters wider than a byte take the direct path only (no shards, no "
+	                                     "partitioned pipeline, no routing)", what);
+}
+
 // Every error return of the host units passes here BEFORE the locals of the failing call are destroyed: it sets the
 // message, drains the device (capi.cpp says why) and returns `code`
 int fail(int code, const char* fmt, ...);

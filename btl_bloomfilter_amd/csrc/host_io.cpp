@@ -152,6 +152,28 @@ int parse_header(FILE* fp, int kind, const char* path, ParsedHeader& out)
 	return BTLBF_OK;
 }
 
+// Does the header of a counting file fit the kind it is loaded as?  BTLBF_COUNTING8 keeps its own rule; a wide kind of w
+// bytes per counter needs BloomFilterSize * w == BloomFilterSizeInBytes -- BitsPerCounter is not trusted for the width (the
+// reference writes 8 for every T, CountingBloomFilter.hpp:109,357).  The reference itself does not check and would
+// silently misread.  No HIP call on the way to the error (the file is the caller's to close).
+int check_counting_header(int kind, const ParsedHeader& ph, const char* path)
+{
+	const uint64_t w = (uint64_t)kind_counter_bytes(kind);
+	if (w == 1) {
+		if (ph.bits_per_counter != 8 || ph.size != ph.size_bytes)
+			return fail(BTLBF_EFORMAT, "%s: only 8-bit counters are supported (BitsPerCounter = %u)", path,
+			            ph.bits_per_counter);
+		return BTLBF_OK;
+	}
+	if (ph.size == 0 || ph.size > ~0ull / w || ph.size * w != ph.size_bytes)
+		return btlbf_set_error(BTLBF_EFORMAT,
+		                       "%s: BloomFilterSize = %llu counters of %llu bytes do not make BloomFilterSizeInBytes = %llu: "
+		                       "not a filter of %llu-bit counters",
+		                       path, (unsigned long long)ph.size, (unsigned long long)w,
+		                       (unsigned long long)ph.size_bytes, (unsigned long long)(8 * w));
+	return BTLBF_OK;
+}
+
 } // namespace
 
 // -------------------------------------------------------------------------------------------------
@@ -178,6 +200,8 @@ extern "C" int btlbf_load(btlbf_filter** out, int kind, const char* path, unsign
 	if (!out || !path)
 		return fail(BTLBF_EINVAL, "null argument");
 	*out = nullptr;
+	if (kind_counter_bytes(kind) < 0)
+		return btlbf_set_error(BTLBF_EINVAL, "unknown filter kind %d", kind);
 	FILE* fp = fopen(path, "rb");
 	if (!fp)
 		return fail(BTLBF_EIO, "error: `%s': %s", path, strerror(errno));
@@ -196,10 +220,9 @@ extern "C" int btlbf_load(btlbf_filter** out, int kind, const char* path, unsign
 		}
 		rc = make_filter(&f, kind, ph.size, ph.size / 8, 0, 1, ph.h, ph.k, 0, device);
 	} else {
-		if (ph.bits_per_counter != 8 || ph.size != ph.size_bytes) {
+		if ((rc = check_counting_header(kind, ph, path))) {
 			fclose(fp);
-			return fail(BTLBF_EFORMAT, "%s: only 8-bit counters are supported (BitsPerCounter = %u)", path,
-			            ph.bits_per_counter);
+			return rc;
 		}
 		rc = make_filter(&f, kind, ph.size, ph.size_bytes, 0, 1, ph.h, ph.k, threshold, device);
 	}
@@ -207,6 +230,7 @@ extern "C" int btlbf_load(btlbf_filter** out, int kind, const char* path, unsign
 		fclose(fp);
 		return rc;
 	}
+	f->bits_per_counter = ph.bits_per_counter; // echoed by store (8 for every 8-bit file, checked above)
 	f->dfpr = ph.dfpr;
 	f->n_entry = ph.n_entry;
 	f->t_entry = ph.t_entry;
@@ -259,6 +283,8 @@ extern "C" int btlbf_create_from_header(btlbf_filter** out, int kind, const char
 	if (!out || !header)
 		return fail(BTLBF_EINVAL, "null argument");
 	*out = nullptr;
+	if (kind_counter_bytes(kind) < 0)
+		return btlbf_set_error(BTLBF_EINVAL, "unknown filter kind %d", kind);
 	FILE* fp = fmemopen(const_cast<char*>(header), len, "rb");
 	if (!fp)
 		return fail(BTLBF_EIO, "fmemopen: %s", strerror(errno));
@@ -273,12 +299,15 @@ extern "C" int btlbf_create_from_header(btlbf_filter** out, int kind, const char
 			return fail(BTLBF_EINVAL, "ERROR: Filter Size \"%llu\" is not a multiple of 8.", (unsigned long long)ph.size);
 		rc = make_filter(&f, kind, ph.size, ph.size / 8, 0, 1, ph.h, ph.k, 0, device);
 	} else {
-		if (ph.bits_per_counter != 8 || ph.size != ph.size_bytes)
+		if (kind == BTLBF_COUNTING8 && (ph.bits_per_counter != 8 || ph.size != ph.size_bytes))
 			return fail(BTLBF_EFORMAT, "only 8-bit counters are supported (BitsPerCounter = %u)", ph.bits_per_counter);
+		if (kind != BTLBF_COUNTING8 && (rc = check_counting_header(kind, ph, "<header>")))
+			return rc;
 		rc = make_filter(&f, kind, ph.size, ph.size_bytes, 0, 1, ph.h, ph.k, threshold, device);
 	}
 	if (rc)
 		return rc;
+	f->bits_per_counter = ph.bits_per_counter;
 	f->dfpr = ph.dfpr;
 	f->n_entry = ph.n_entry;
 	f->t_entry = ph.t_entry;
@@ -323,9 +352,19 @@ static int write_body(const btlbf_filter* f, int fd, uint64_t file_off, const ch
 	return rc;
 }
 
+static int store_locked(btlbf_filter* f, const char* path);
+
 extern "C" int btlbf_store_shard(btlbf_filter* f, const char* path)
 {
 	FilterLock lk__(f);
+	if (f && is_wide(f))
+		return refuse_wide("btlbf_store_shard");
+	return store_locked(f, path);
+}
+
+// header + body of the local array at its place in the file; the caller holds the filter's lock
+static int store_locked(btlbf_filter* f, const char* path)
+{
 	if (!f || !path)
 		return fail(BTLBF_EINVAL, "null argument");
 	DeviceGuard g(f->device);
@@ -355,5 +394,5 @@ extern "C" int btlbf_store(btlbf_filter* f, const char* path)
 	FilterLock lk__(f);
 	if (f && f->shard_count != 1)
 		return fail(BTLBF_EINVAL, "btlbf_store on a shard: use btlbf_store_shard");
-	return btlbf_store_shard(f, path);
+	return store_locked(f, path);
 }

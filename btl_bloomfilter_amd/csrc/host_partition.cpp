@@ -824,6 +824,8 @@ extern "C" int btlbf_route_plan(btlbf_filter* f, uint64_t len, const btlbf_layou
                                 uint64_t* ent_bytes_per_shard, uint64_t* cnt_bytes_per_shard)
 {
 	FilterLock lk__(f);
+	if (f && is_wide(f))
+		return refuse_wide("btlbf_route_plan");
 	if (!f || !ent_bytes_per_shard || !cnt_bytes_per_shard)
 		return fail(BTLBF_EINVAL, "null argument");
 	RoutePlan rp;
@@ -855,6 +857,8 @@ extern "C" int btlbf_route_windows(btlbf_filter* f, unsigned n_shards, unsigned*
                                    unsigned* shards_per_window)
 {
 	FilterLock lk__(f);
+	if (f && is_wide(f))
+		return refuse_wide("btlbf_route_windows");
 	if (!f || !n_windows || !shards_per_window)
 		return fail(BTLBF_EINVAL, "null argument");
 	RoutePlan rp;
@@ -871,6 +875,8 @@ extern "C" int btlbf_route_seqs(btlbf_filter* f, const char* seq, uint64_t len, 
                                 uint64_t* spill_list, uint64_t spill_cap, uint64_t* spill_count, void* stream)
 {
 	FilterLock lk__(f);
+	if (f && is_wide(f))
+		return refuse_wide("btlbf_route_seqs");
 	int rc = seq_precheck(f);
 	if (rc)
 		return rc;
@@ -915,6 +921,8 @@ extern "C" int btlbf_route_geometry(btlbf_filter* f, uint64_t plan_len, const bt
                                     unsigned n_blocks, uint32_t* out4)
 {
 	FilterLock lk__(f);
+	if (f && is_wide(f))
+		return refuse_wide("btlbf_route_geometry");
 	if (!f || !out4)
 		return fail(BTLBF_EINVAL, "null argument");
 	RoutePlan rp;
@@ -931,6 +939,8 @@ extern "C" int btlbf_owner_scratch_bytes(btlbf_filter* f, uint64_t plan_len, con
                                          unsigned n_blocks, uint64_t* bytes)
 {
 	FilterLock lk__(f);
+	if (f && is_wide(f))
+		return refuse_wide("btlbf_owner_scratch_bytes");
 	if (!f || !bytes)
 		return fail(BTLBF_EINVAL, "null argument");
 	RoutePlan rp;
@@ -946,6 +956,8 @@ extern "C" int btlbf_apply_routed_bins(btlbf_filter* f, const void* recv_ent, co
                                        uint64_t fail_cap, uint64_t* fail_count, void* stream)
 {
 	FilterLock lk__(f);
+	if (f && is_wide(f))
+		return refuse_wide("btlbf_apply_routed_bins");
 	RoutePlan rp;
 	if (int rc = plan_routed(f, plan_len, layout_params(layout), n_shards, n_blocks, true, rp))
 		return rc;
@@ -958,6 +970,8 @@ extern "C" int btlbf_apply_routed(btlbf_filter* f, const void* recv_ent, const v
                                   uint64_t* fail_list, uint64_t fail_cap, uint64_t* fail_count, void* stream)
 {
 	FilterLock lk__(f);
+	if (f && is_wide(f))
+		return refuse_wide("btlbf_apply_routed");
 	RoutePlan rp;
 	if (int rc = plan_routed(f, plan_len, layout_params(layout), n_shards, n_blocks, true, rp))
 		return rc;
@@ -969,6 +983,8 @@ extern "C" int btlbf_apply_spill(btlbf_filter* f, const uint64_t* global_pos, ui
                                  uint64_t* fail_list, uint64_t fail_cap, uint64_t* fail_count, void* stream)
 {
 	FilterLock lk__(f);
+	if (f && is_wide(f))
+		return refuse_wide("btlbf_apply_spill");
 	if (!f || (n && !global_pos))
 		return fail(BTLBF_EINVAL, "null argument");
 	DeviceGuard g(f->device);
@@ -986,6 +1002,8 @@ extern "C" int btlbf_resolve_seqs(btlbf_filter* f, const char* seq, uint64_t len
                                   const uint64_t* fail_list, uint64_t n_fail, uint64_t* hit_bits, void* stream)
 {
 	FilterLock lk__(f);
+	if (f && is_wide(f))
+		return refuse_wide("btlbf_resolve_seqs");
 	int rc = seq_precheck(f);
 	if (rc)
 		return rc;

@@ -32,9 +32,16 @@ int seq_precheck(const btlbf_filter* f)
 
 namespace {
 
+// the one whole-buffer launch of a query flavour: the fused kernel of the filter's counter width
+hipError_t launch_query(const btlbf_filter* f, int op, const SeqArgs& a, hipStream_t s)
+{
+	return is_wide(f) ? launch_wide_seq_op(W_QUERY, (int)counter_bytes(f), a, s) : launch_seq_op(op, a, s);
+}
+
+// min_out: len elements of min_width bytes each (the filter's counter width; 1 for the byte forms)
 int run_query_like(btlbf_filter* f, int op, const char* seq, uint64_t len, const btlbf_layout* layout,
-                   uint64_t* hit_bits, uint64_t* valid_bits, uint64_t* counts, uint8_t* min_out, int mem,
-                   void* stream, FilterLock* lk = nullptr)
+                   uint64_t* hit_bits, uint64_t* valid_bits, uint64_t* counts, void* min_out, int mem,
+                   void* stream, FilterLock* lk = nullptr, unsigned min_width = 1)
 {
 	int rc = seq_precheck(f);
 	if (rc)
@@ -56,7 +63,7 @@ int run_query_like(btlbf_filter* f, int op, const char* seq, uint64_t len, const
 	{
 		const uint64_t up16 = ~(uint64_t)15, bm = (bitmap_bytes(len) + 15) & up16;
 		const uint64_t o_hit = (len + 16 + 15) & up16, o_valid = o_hit + bm, o_cnt = o_valid + bm, o_min = o_cnt + 16,
-		               o_end = o_min + ((len + 15) & up16);
+		               o_end = o_min + ((len * min_width + 15) & up16);
 		if (mem == BTLBF_HOST && len && len <= 65536 && (!layout || !layout->starts) && o_end <= Mailbox::kBytes &&
 		    mailbox().get()) {
 			if ((rc = check_layout(layout, len)))
@@ -72,7 +79,7 @@ int run_query_like(btlbf_filter* f, int op, const char* seq, uint64_t len, const
 			a.valid_bits = valid_bits || counts ? mb.dev + o_valid : nullptr;
 			a.min_out = min_out ? mb.dev + o_min : nullptr;
 			REQUIRE_MATERIALIZED(f);
-			HIP_TRY(launch_seq_op(op, a, s));
+			HIP_TRY(launch_query(f, op, a, s));
 			if (lk && op != OP_BF_INSERT_CHECK)
 				lk->release(); // a read-only call only waits from here on (its mailbox is the calling thread's own)
 			HIP_TRY(hipStreamSynchronize(s));
@@ -90,7 +97,7 @@ int run_query_like(btlbf_filter* f, int op, const char* seq, uint64_t len, const
 				}
 			}
 			if (min_out)
-				memcpy(min_out, mb.host + o_min, len);
+				memcpy(min_out, mb.host + o_min, len * min_width);
 			return BTLBF_OK;
 		}
 	}
@@ -105,7 +112,7 @@ int run_query_like(btlbf_filter* f, int op, const char* seq, uint64_t len, const
 		return rc;
 	if ((rc = ob_cnt.prepare(counts, 16, mem, true, s)))
 		return rc;
-	if ((rc = ob_min.prepare(min_out, len, mem, false, s)))
+	if ((rc = ob_min.prepare(min_out, len * min_width, mem, false, s)))
 		return rc;
 	SeqArgs a = base_args(f, v, len);
 	a.hit_bits = static_cast<uint8_t*>(ob_hit.d);
@@ -113,14 +120,15 @@ int run_query_like(btlbf_filter* f, int op, const char* seq, uint64_t len, const
 	a.counts = static_cast<uint64_t*>(ob_cnt.d);
 	a.min_out = static_cast<uint8_t*>(ob_min.d);
 	bool answered = false;
-	if (op == OP_BF_CONTAINS || op == OP_BF_CONTAINS_WIN || (op == OP_CBF_QUERY && !min_out)) { // minimum counts need the values: direct
+	// minimum counts need the values, and wide counters have the direct path only: neither is routed
+	if (!is_wide(f) && (op == OP_BF_CONTAINS || op == OP_BF_CONTAINS_WIN || (op == OP_CBF_QUERY && !min_out))) {
 		if ((rc = contains_routed(f, a, op, s, &answered)))
 			return rc;
 	}
 	if (!answered) {
 		REQUIRE_MATERIALIZED(f);
 		ProfSpan ps(f, op == OP_BF_CONTAINS || op == OP_BF_CONTAINS_WIN ? BTLBF_PROF_QUERY_DIRECT : BTLBF_PROF_OTHER, s);
-		HIP_TRY(launch_seq_op(op, a, s));
+		HIP_TRY(launch_query(f, op, a, s));
 	}
 	if ((rc = ob_hit.finish(s)) || (rc = ob_valid.finish(s)) || (rc = ob_cnt.finish(s)) ||
 	    (rc = ob_min.finish(s)))
@@ -130,8 +138,19 @@ int run_query_like(btlbf_filter* f, int op, const char* seq, uint64_t len, const
 	return BTLBF_OK;
 }
 
-int run_hash_rows(btlbf_filter* f, int hop, const uint64_t* hashes, uint64_t n, uint8_t* out, int serial,
-                  int mem, void* stream, FilterLock* lk = nullptr)
+// the launch of a hash-row operation on the filter's counter width (row_valid: raw k-mers without a defined value)
+hipError_t launch_rows(const btlbf_filter* f, int hop, const uint64_t* rows, uint64_t n, void* out, int serial,
+                       hipStream_t s, const uint8_t* row_valid = nullptr)
+{
+	if (is_wide(f))
+		return launch_wide_hash_op(hop, (int)counter_bytes(f), f->d_data, f->mod, f->h, f->thr, rows, n, out, serial, s,
+		                           row_valid);
+	return launch_hash_op(hop, f->d_data, f->mod, f->h, f->thr, rows, n, static_cast<uint8_t*>(out), serial, s, row_valid);
+}
+
+// out: n elements of out_width bytes each (1, or the counter width for the minimum counts of a wide filter)
+int run_hash_rows(btlbf_filter* f, int hop, const uint64_t* hashes, uint64_t n, void* out, int serial,
+                  int mem, void* stream, FilterLock* lk = nullptr, unsigned out_width = 1)
 {
 	if (!f)
 		return fail(BTLBF_EINVAL, "null filter");
@@ -145,17 +164,17 @@ int run_hash_rows(btlbf_filter* f, int hop, const uint64_t* hashes, uint64_t n, 
 	// a few rows from host memory (the shims' per-k-mer contains / insertAndCheck / minCount): through the calling
 	// thread's pinned mailbox -- no staging buffers, no copies, one launch and one synchronisation
 	const uint64_t row_bytes = (n * f->h * 8 + 15) & ~(uint64_t)15;
-	if (mem == BTLBF_HOST && n && row_bytes + n <= Mailbox::kBytes && mailbox().get()) {
+	if (mem == BTLBF_HOST && n && row_bytes + n * out_width <= Mailbox::kBytes && mailbox().get()) {
 		Mailbox& mb = mailbox();
 		memcpy(mb.host, hashes, n * f->h * 8);
 		REQUIRE_MATERIALIZED(f);
-		HIP_TRY(launch_hash_op(hop, f->d_data, f->mod, f->h, f->thr, reinterpret_cast<const uint64_t*>(mb.dev), n,
-		                       out ? mb.dev + row_bytes : nullptr, serial, s));
+		HIP_TRY(launch_rows(f, hop, reinterpret_cast<const uint64_t*>(mb.dev), n, out ? mb.dev + row_bytes : nullptr, serial,
+		                    s));
 		if (lk && (hop == H_BF_CONTAINS || hop == H_CBF_CONTAINS || hop == H_CBF_MIN))
 			lk->release(); // the mailbox and (with BTLBF_STREAM_PER_THREAD) the stream are the calling thread's own
 		HIP_TRY(hipStreamSynchronize(s));
 		if (out)
-			memcpy(out, mb.host + row_bytes, n);
+			memcpy(out, mb.host + row_bytes, n * out_width);
 		return BTLBF_OK;
 	}
 	DevBuf hb;
@@ -167,11 +186,11 @@ int run_hash_rows(btlbf_filter* f, int hop, const uint64_t* hashes, uint64_t n, 
 		d_h = hb.as<uint64_t>();
 	}
 	OutBuf ob;
-	int rc = ob.prepare(out, n, mem, false, s);
+	int rc = ob.prepare(out, n * out_width, mem, false, s);
 	if (rc)
 		return rc;
 	REQUIRE_MATERIALIZED(f);
-	HIP_TRY(launch_hash_op(hop, f->d_data, f->mod, f->h, f->thr, d_h, n, static_cast<uint8_t*>(ob.d), serial, s));
+	HIP_TRY(launch_rows(f, hop, d_h, n, ob.d, serial, s));
 	if ((rc = ob.finish(s)))
 		return rc;
 	if (mem == BTLBF_HOST)
@@ -218,8 +237,7 @@ int run_kmer_rows(btlbf_filter* f, int hop, const char* kmers, uint64_t n, uint8
 	OutBuf ob;
 	if ((rc = ob.prepare(out, n, mem, false, s)))
 		return rc;
-	HIP_TRY(launch_hash_op(hop, f->d_data, f->mod, f->h, f->thr, kr.rows.as<uint64_t>(), n, static_cast<uint8_t*>(ob.d),
-	                       serial, s, kr.valid.as<uint8_t>()));
+	HIP_TRY(launch_rows(f, hop, kr.rows.as<uint64_t>(), n, ob.d, serial, s, kr.valid.as<uint8_t>()));
 	if ((rc = ob.finish(s)))
 		return rc;
 	HIP_TRY(hipStreamSynchronize(s)); // the temporaries are freed on return
@@ -285,8 +303,12 @@ extern "C" int btlbf_insert_seqs(btlbf_filter* f, const char* seq, uint64_t len,
 			a.hashes = hashes.as<uint64_t>();
 			a.valid_bits = valid.as<uint8_t>();
 			HIP_TRY(launch_seq_op(OP_HASH_ONLY, a, s));
-			HIP_TRY(launch_serial_seq_update(a, op == BTLBF_INCREMENT_MIN ? H_CBF_INC_MIN : H_CBF_INC_ALL,
-			                                 hashes.as<uint64_t>(), valid.as<uint8_t>(), nullptr, s));
+			const int hop = op == BTLBF_INCREMENT_MIN ? H_CBF_INC_MIN : H_CBF_INC_ALL;
+			if (is_wide(f))
+				HIP_TRY(launch_wide_serial_seq_update((int)counter_bytes(f), a, hop, hashes.as<uint64_t>(),
+				                                      valid.as<uint8_t>(), s));
+			else
+				HIP_TRY(launch_serial_seq_update(a, hop, hashes.as<uint64_t>(), valid.as<uint8_t>(), nullptr, s));
 			HIP_TRY(hipStreamSynchronize(s));
 			return BTLBF_OK;
 		}
@@ -294,7 +316,10 @@ extern "C" int btlbf_insert_seqs(btlbf_filter* f, const char* seq, uint64_t len,
 	{
 		REQUIRE_MATERIALIZED(f);
 		ProfSpan ps(f, kop == OP_BF_INSERT ? BTLBF_PROF_INSERT_DIRECT : BTLBF_PROF_OTHER, s);
-		HIP_TRY(launch_seq_op(kop, a, s));
+		if (is_wide(f))
+			HIP_TRY(launch_wide_seq_op(kop == OP_CBF_INC_MIN ? W_INC_MIN : W_INC_ALL, (int)counter_bytes(f), a, s));
+		else
+			HIP_TRY(launch_seq_op(kop, a, s));
 	}
 	if (mem == BTLBF_HOST)
 		HIP_TRY(hipStreamSynchronize(s));
@@ -332,9 +357,24 @@ extern "C" int btlbf_min_count_seqs(btlbf_filter* f, const char* seq, uint64_t l
 	FilterLock lk__(f);
 	if (!f)
 		return fail(BTLBF_EINVAL, "null filter");
+	if (is_wide(f)) // before any HIP call, nothing written: the caller's bytes would be overrun
+		return btlbf_set_error(BTLBF_EINVAL, "btlbf_min_count_seqs: the filter's counters have %u bytes, use "
+		                                     "btlbf_min_count_seqs_wide", counter_bytes(f));
 	if (f->kind != BTLBF_COUNTING8)
 		return fail(BTLBF_EINVAL, "min_count needs a counting filter");
 	return run_query_like(f, OP_CBF_QUERY, seq, len, layout, nullptr, valid_bits, nullptr, min_out, mem, stream);
+}
+
+extern "C" int btlbf_min_count_seqs_wide(btlbf_filter* f, const char* seq, uint64_t len, const btlbf_layout* layout,
+                                         void* min_out, uint64_t* valid_bits, int mem, void* stream)
+{
+	FilterLock lk__(f);
+	if (!f)
+		return fail(BTLBF_EINVAL, "null filter");
+	if (!is_counting(f))
+		return fail(BTLBF_EINVAL, "min_count needs a counting filter");
+	return run_query_like(f, OP_CBF_QUERY, seq, len, layout, nullptr, valid_bits, nullptr, min_out, mem, stream, nullptr,
+	                      counter_bytes(f));
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -347,12 +387,12 @@ extern "C" int btlbf_insert_hashes(btlbf_filter* f, const uint64_t* hashes, uint
 	if (!f)
 		return fail(BTLBF_EINVAL, "null filter");
 	int hop = H_BF_INSERT;
-	if (f->kind == BTLBF_COUNTING8) {
+	if (is_counting(f)) {
 		if (op != BTLBF_INCREMENT_MIN && op != BTLBF_INCREMENT_ALL)
 			return fail(BTLBF_EINVAL, "op must be BTLBF_INCREMENT_MIN or BTLBF_INCREMENT_ALL");
 		hop = op == BTLBF_INCREMENT_MIN ? H_CBF_INC_MIN : H_CBF_INC_ALL;
 	}
-	const int serial = f->kind == BTLBF_COUNTING8 && order == BTLBF_ORDER_SERIAL;
+	const int serial = is_counting(f) && order == BTLBF_ORDER_SERIAL;
 	return run_hash_rows(f, hop, hashes, n, nullptr, serial, mem, stream);
 }
 
@@ -382,9 +422,23 @@ extern "C" int btlbf_min_count_hashes(btlbf_filter* f, const uint64_t* hashes, u
 	FilterLock lk__(f);
 	if (!f || !min_out)
 		return fail(BTLBF_EINVAL, "null argument");
+	if (is_wide(f)) // before any HIP call, nothing written
+		return btlbf_set_error(BTLBF_EINVAL, "btlbf_min_count_hashes: the filter's counters have %u bytes, use "
+		                                     "btlbf_min_count_hashes_wide", counter_bytes(f));
 	if (f->kind != BTLBF_COUNTING8)
 		return fail(BTLBF_EINVAL, "min_count needs a counting filter");
 	return run_hash_rows(f, H_CBF_MIN, hashes, n, min_out, 0, mem, stream);
+}
+
+extern "C" int btlbf_min_count_hashes_wide(btlbf_filter* f, const uint64_t* hashes, uint64_t n, void* min_out, int mem,
+                                           void* stream)
+{
+	FilterLock lk__(f);
+	if (!f || !min_out)
+		return fail(BTLBF_EINVAL, "null argument");
+	if (!is_counting(f))
+		return fail(BTLBF_EINVAL, "min_count needs a counting filter");
+	return run_hash_rows(f, H_CBF_MIN, hashes, n, min_out, 0, mem, stream, nullptr, counter_bytes(f));
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -397,12 +451,12 @@ extern "C" int btlbf_insert_kmers(btlbf_filter* f, const char* kmers, uint64_t n
 	if (!f)
 		return fail(BTLBF_EINVAL, "null filter");
 	int hop = H_BF_INSERT;
-	if (f->kind == BTLBF_COUNTING8) {
+	if (is_counting(f)) {
 		if (op != BTLBF_INCREMENT_MIN && op != BTLBF_INCREMENT_ALL)
 			return fail(BTLBF_EINVAL, "op must be BTLBF_INCREMENT_MIN or BTLBF_INCREMENT_ALL");
 		hop = op == BTLBF_INCREMENT_MIN ? H_CBF_INC_MIN : H_CBF_INC_ALL;
 	}
-	const int serial = f->kind == BTLBF_COUNTING8 && order == BTLBF_ORDER_SERIAL;
+	const int serial = is_counting(f) && order == BTLBF_ORDER_SERIAL;
 	return run_kmer_rows(f, hop, kmers, n, nullptr, serial, mem, stream);
 }
 

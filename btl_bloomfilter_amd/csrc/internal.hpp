@@ -409,4 +409,21 @@ hipError_t launch_mibf_tally(const void* hits, const uint32_t* n_hits, const uin
                              const uint32_t* eval_count, uint64_t n_rows, uint32_t max_results, uint64_t n_ids,
                              unsigned long long* best, unsigned long long* any, unsigned long long* totals, hipStream_t s);
 
+// counting filters with 16-, 32- and 64-bit counters (wide_counter_kernels.hip; `bytes` = 2, 4 or 8, the array holds
+// mod.size counters of that width).  Direct path only: one fused launch per sequence call, whole filters, no shards.
+enum WideSeqOp : int { W_QUERY = 0, W_INC_ALL = 1, W_INC_MIN = 2 };
+// a.min_out (W_QUERY, optional): a.len elements of `bytes` bytes each
+hipError_t launch_wide_seq_op(int op, int bytes, const SeqArgs& a, hipStream_t s);
+// op: a counting HashOp (H_CBF_*); out: n elements of `bytes` bytes for H_CBF_MIN, n bytes for the others
+hipError_t launch_wide_hash_op(int op, int bytes, void* filter, const ModParams& mod, uint32_t h, uint32_t threshold,
+                               const uint64_t* hashes, uint64_t n, void* out, int serial, hipStream_t s,
+                               const uint8_t* row_valid = nullptr);
+hipError_t launch_wide_serial_seq_update(int bytes, const SeqArgs& a, int op, const uint64_t* hashes,
+                                         const uint8_t* valid_bits, hipStream_t s);
+// mode 1: non-zero counters, 2: counters >= threshold; nbytes a multiple of 16
+hipError_t launch_wide_popcount(const void* data, uint64_t nbytes, int bytes, int mode, uint32_t threshold,
+                                unsigned long long* out, hipStream_t s);
+hipError_t launch_wide_compare(const void* a, const void* b, uint64_t nbytes, int bytes, unsigned long long* out3,
+                               hipStream_t s);
+
 } // namespace btlbf

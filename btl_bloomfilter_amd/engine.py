@@ -135,18 +135,19 @@ class _Filter(_Owned):
 
     # -- lifetime --------------------------------------------------------------------------
     @classmethod
-    def _create(cls, size, hash_num, kmer_size, threshold=0, device=0):
+    def _create(cls, size, hash_num, kmer_size, threshold=0, device=0, kind=None):
         L = _lib.load()
         h = C.c_void_p()
-        check(L.btlbf_create(C.byref(h), cls.kind, int(size), int(hash_num), int(kmer_size), int(threshold),
-                             int(device)))
+        check(L.btlbf_create(C.byref(h), cls.kind if kind is None else kind, int(size), int(hash_num), int(kmer_size),
+                             int(threshold), int(device)))
         return h
 
     @classmethod
-    def _load(cls, path, threshold=0, device=0):
+    def _load(cls, path, threshold=0, device=0, kind=None):
         L = _lib.load()
         h = C.c_void_p()
-        check(L.btlbf_load(C.byref(h), cls.kind, str(path).encode(), int(threshold), int(device)))
+        check(L.btlbf_load(C.byref(h), cls.kind if kind is None else kind, str(path).encode(), int(threshold),
+                           int(device)))
         return h
 
     # -- attributes (reference getters) ------------------------------------------------------
@@ -191,7 +192,7 @@ class _Filter(_Owned):
 
     def compare(self, other):
         """(positions that differ, positions where self > other, where self < other) against another filter
-        of the same geometry, computed in HBM (btlbf_compare); positions are bits or uint8_t counters"""
+        of the same geometry, computed in HBM (btlbf_compare); positions are bits or counters of the filter's width"""
         out = (C.c_uint64 * 3)()
         check(self._L.btlbf_compare(self._h, other._h, out))
         return tuple(out)
@@ -275,9 +276,9 @@ class _Filter(_Owned):
         a = np.ascontiguousarray(hashes, dtype=np.uint64).reshape(-1, h)
         return _Buf(a, np.uint64), a.shape[0]
 
-    def _rows_out(self, fn, hashes, *extra, stream=None):
+    def _rows_out(self, fn, hashes, *extra, stream=None, dtype=np.uint8):
         b, n = self._rows(hashes)
-        out, optr = _out(b, n, np.uint8)
+        out, optr = _out(b, n, dtype)
         check(fn(self._h, b.ptr, n, optr, *extra, b.mem, _stream_ptr(stream, b.keep)))
         return out
 
@@ -454,15 +455,30 @@ def insertSeq(bloom, seq, numHashes=None, k=None):
 
 
 class CountingBloomFilter(_Filter):
-    """uint8_t counting filter (reference: /root/reference/CountingBloomFilter.hpp, T = uint8_t)"""
+    """counting filter (reference: CountingBloomFilter.hpp, CountingBloomFilter<T>): counter_bits = 8 (T = uint8_t, the
+    default), 16, 32 or 64.  The wide kinds take the direct path only (include/btlbf.h); minimum counts and
+    counters() come in the counter's dtype."""
 
     kind = COUNTING8
 
-    def __init__(self, sizeInBytes=None, hashNum=None, kmerSize=None, countThreshold=0, path=None, device=0):
+    def __init__(self, sizeInBytes=None, hashNum=None, kmerSize=None, countThreshold=0, path=None, device=0,
+                 counter_bits=8):
+        if counter_bits not in _lib.COUNTING_KIND:
+            raise ValueError("counter_bits must be 8, 16, 32 or 64")
+        kind = _lib.COUNTING_KIND[counter_bits]
+        self.counter_bits = counter_bits
+        self.dtype = np.dtype("<u%d" % (counter_bits // 8))
         if path is not None:
-            super().__init__(self._load(path, countThreshold, device))
+            super().__init__(self._load(path, countThreshold, device, kind))
         else:
-            super().__init__(self._create(sizeInBytes, hashNum, kmerSize, countThreshold, device))
+            super().__init__(self._create(sizeInBytes, hashNum, kmerSize, countThreshold, device, kind))
+
+    def counterBytes(self):
+        return self._L.btlbf_counter_bytes(self._h)
+
+    def counters(self):
+        """the downloaded body viewed in the counter's dtype: size() counters"""
+        return self.download().view(self.dtype)
 
     def size(self):
         return self._L.btlbf_size(self._h)
@@ -502,7 +518,9 @@ class CountingBloomFilter(_Filter):
                                           _stream_ptr(stream, b.keep)))
 
     def minCount(self, hashes, stream=None):
-        return self._rows_out(self._L.btlbf_min_count_hashes, hashes, stream=stream)
+        if self.counter_bits == 8:
+            return self._rows_out(self._L.btlbf_min_count_hashes, hashes, stream=stream)
+        return self._rows_out(self._L.btlbf_min_count_hashes_wide, hashes, stream=stream, dtype=self.dtype)
 
     def contains(self, hashes, stream=None):
         return self._rows_out(self._L.btlbf_contains_hashes, hashes, stream=stream)
@@ -519,11 +537,25 @@ class CountingBloomFilter(_Filter):
         b = _Buf(seq)
         lay, keep = _layout(starts, read_len, b.mem)
         n = b.nbytes
-        mn, p1 = _out(b, n, np.uint8)
+        mn, p1 = _out(b, n, self.dtype)
         valid, p2 = _out(b, _words(n), np.uint64)
-        check(self._L.btlbf_min_count_seqs(self._h, b.ptr, n, C.byref(lay) if lay else None, p1, p2, b.mem,
-                                           _stream_ptr(stream, b.keep)))
+        fn = self._L.btlbf_min_count_seqs if self.counter_bits == 8 else self._L.btlbf_min_count_seqs_wide
+        check(fn(self._h, b.ptr, n, C.byref(lay) if lay else None, p1, p2, b.mem, _stream_ptr(stream, b.keep)))
         return mn, valid
+
+    # raw k-mers (btlbf_insert_kmers / btlbf_contains_kmers): n k-mers of kmerSize bytes each, back to back
+    def insertKmers(self, kmers, increment_all=False, serial=False, stream=None):
+        b = _Buf(kmers)
+        check(self._L.btlbf_insert_kmers(self._h, b.ptr, b.nbytes // self.getKmerSize(),
+                                         INCREMENT_ALL if increment_all else INCREMENT_MIN,
+                                         ORDER_SERIAL if serial else ORDER_PARALLEL, b.mem, _stream_ptr(stream, b.keep)))
+
+    def containsKmers(self, kmers, stream=None):
+        b = _Buf(kmers)
+        n = b.nbytes // self.getKmerSize()
+        out, optr = _out(b, n, np.uint8)
+        check(self._L.btlbf_contains_kmers(self._h, b.ptr, n, optr, b.mem, _stream_ptr(stream, b.keep)))
+        return out
 
 
 class RankSupport(_Owned):

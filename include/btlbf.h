@@ -64,7 +64,11 @@ extern "C" {
 typedef struct btlbf_filter btlbf_filter; /* opaque; owns its HBM array (BloomFilter.hpp:381,398) */
 
 enum { BTLBF_HOST = 0, BTLBF_DEVICE = 1 };
-enum { BTLBF_BLOOM = 0, BTLBF_COUNTING8 = 1 };
+/* BTLBF_COUNTING8 / 16 / 32 / 64: CountingBloomFilter<T> with T = uint8_t / uint16_t / uint32_t / uint64_t.  The kinds
+ * wider than a byte ("wide") take the DIRECT path only: every sequence call is one fused launch on the whole filter.
+ * Shards, the partitioned pipeline, the position and routing calls and btlbf_microbench return BTLBF_EINVAL for them
+ * before any HIP call; each entry says so where it applies. */
+enum { BTLBF_BLOOM = 0, BTLBF_COUNTING8 = 1, BTLBF_COUNTING16 = 2, BTLBF_COUNTING32 = 3, BTLBF_COUNTING64 = 4 };
 enum {
 	BTLBF_OK = 0,
 	BTLBF_EINVAL = 1,  /* bad argument (e.g. bit count not a multiple of 8, BloomFilter.hpp:391-394) */
@@ -79,22 +83,25 @@ enum { BTLBF_INCREMENT_MIN = 0, BTLBF_INCREMENT_ALL = 1 };
  * way incrementMin is reproducible (it is order-dependent).
  *
  * BTLBF_ORDER_PARALLEL runs one k-mer per lane.  What a call then guarantees is what EVERY interleaving of the
- * reference's per-probe atomics (CountingBloomFilter.hpp:135-183: byte loads and byte compare-and-swaps) can
- * produce, and nothing more (tests/update_order_model.py states it as checkers):
+ * reference's per-probe atomics (CountingBloomFilter.hpp:135-183: counter loads and counter compare-and-swaps) can
+ * produce, and nothing more (tests/update_order_model.py states it as checkers; tests/wide_counter_model.py restates
+ * them for every width).  MAX = 2^bits - 1 is the largest value of the filter's counter: 255, 65535, 2^32 - 1, 2^64 - 1:
  *   incrementAll: exact.  Saturating +1 commutes, so the counters are those of the serial order.
  *   incrementMin, counters before -> after one call, K = clean k-mers of the call, each with its h counters:
- *     - no counter decreases, a counter at 255 stays at 255, a counter that no k-mer of the call probes is unchanged
- *       (the four counters of a 32-bit word are updated with a word compare-and-swap that never carries);
+ *     - no counter decreases, a counter at MAX stays at MAX, a counter that no k-mer of the call probes is unchanged
+ *       (8-bit counters: the four counters of a 32-bit word are updated with a word compare-and-swap that never
+ *       carries; 16-bit counters are updated with a 32-bit compare-and-swap on the word that holds two of them, and
+ *       it never carries into the neighbour; 32- and 64-bit counters with a compare-and-swap on the counter itself);
  *     - after <= what incrementAll of the same call would give, counter by counter;
- *     - for every k-mer present: min(after[its counters]) >= min(min(before[its counters]) + 1, 255).  One call
+ *     - for every k-mer present: min(after[its counters]) >= min(min(before[its counters]) + 1, MAX).  One call
  *       raises the minimum of a k-mer that occurs in it by AT LEAST ONE, not by its multiplicity.  An insert is done
  *       once ONE of its compare-and-swaps m -> m + 1 has made the change (one that changed nothing reads the minimum
  *       again and retries).  With h >= 2, two concurrent inserts of one k-mer may both read the minimum m and each
  *       win the compare-and-swap on a DIFFERENT counter of the k-mer, losing it on the other's: both are done, and
  *       every counter stands at m + 1 after two occurrences -- in the reference as well.  With h = 1 there is one
- *       counter to win, so the minimum rises by the full multiplicity (up to 255).  Callers that need
+ *       counter to win, so the minimum rises by the full multiplicity (up to MAX).  Callers that need
  *       "n occurrences -> minimum >= n" with h >= 2 use incrementAll or the serial order;
- *     - while no touched counter reaches 255: |K| <= sum(after) - sum(before) <= h * |K|.
+ *     - while no touched counter reaches MAX: |K| <= sum(after) - sum(before) <= h * |K|.
  *   insertAndCheck on a counting filter: out = 1 where the minimum before the call is >= threshold, out = 0 where
  *     the minimum in incrementAll's result is < threshold, either answer in between; the counters as incrementMin. */
 enum { BTLBF_ORDER_PARALLEL = 0, BTLBF_ORDER_SERIAL = 1 };
@@ -117,6 +124,10 @@ int btlbf_device_count(void); /* number of visible GPUs, 0 if none (never fails)
  * BTLBF_COUNTING8: `size` = bytes requested, rounded up to a multiple of 8; one uint8_t counter
  *                  per byte (CountingBloomFilter<uint8_t>(size_t,unsigned,unsigned,unsigned),
  *                  CountingBloomFilter.hpp:31-50).  `threshold` is ignored for BTLBF_BLOOM.
+ * BTLBF_COUNTING16 / 32 / 64: the same constructor for the wider T: `size` = bytes requested, rounded up to a multiple
+ *                  of 8 = sizeInBytes(); btlbf_size() = sizeInBytes() / sizeof(T) counters, and positions are
+ *                  hash % btlbf_size() -- the counter count, not the byte count (CountingBloomFilter.hpp:40-58).
+ *                  `threshold` stays unsigned and is compared against the full-width minimum.
  * The array is allocated in the HBM of `device` and zeroed. */
 int btlbf_create(btlbf_filter** out, int kind, uint64_t size, unsigned hash_num, unsigned kmer_size,
                  unsigned threshold, int device);
@@ -129,6 +140,7 @@ int btlbf_create(btlbf_filter** out, int kind, uint64_t size, unsigned hash_num,
  * shards that are each handed the same reads build the single filter's body, and the AND of their
  * answers is the single filter's contains() ("gather mode" of btl_bloomfilter_amd/sharded.py: moves
  * reads instead of probes between GPUs).  Both take the partitioned pipeline like an unsharded filter. */
+/* (wide counting kinds: EINVAL -- no shards) */
 int btlbf_create_shard(btlbf_filter** out, int kind, uint64_t global_size, unsigned shard_index,
                        unsigned shard_count, unsigned hash_num, unsigned kmer_size,
                        unsigned threshold, int device);
@@ -138,7 +150,13 @@ int btlbf_destroy(btlbf_filter* f); /* ~BloomFilter, BloomFilter.hpp:381 */
  * load:  BloomFilter(const string&) BloomFilter.hpp:101-116,118-166;
  *        CountingBloomFilter(const string&, unsigned) CountingBloomFilter.hpp:262-343
  * store: storeFilter BloomFilter.hpp:304-314 / CountingBloomFilter.hpp:331-342; the header bytes
- *        are those the reference writes (key order, tab indent, %#.17g doubles) */
+ *        are those the reference writes (key order, tab indent, %#.17g doubles)
+ * Counting files of every width share one magic line, and the reference writes BitsPerCounter = 8 whatever T is (the
+ * member is only ever changed by loadHeader, CountingBloomFilter.hpp:109,328,357): a created filter writes 8, a loaded
+ * filter echoes what its file said, and the field is not trusted for the width.  The width is the `kind` the caller
+ * loads with, as T is in the reference -- which does not check that the header fits T; here a load (or
+ * create_from_header) with a counting kind of width w requires BloomFilterSize * w == BloomFilterSizeInBytes and
+ * otherwise returns BTLBF_EFORMAT before any HIP call, the message naming both numbers. */
 int btlbf_load(btlbf_filter** out, int kind, const char* path, unsigned threshold, int device);
 /* header text only (everything up to and including the "[HeaderEnd]" line) -> a zeroed filter of that geometry
  * with nEntry / Entry / dFPR taken over: what the reference's public loadHeader(std::istream&) leaves behind
@@ -154,6 +172,7 @@ int btlbf_store_shard(btlbf_filter* f, const char* path);
 
 /* ---- attributes (getters of BloomFilter.hpp:325-327,369-379; CountingBloomFilter.hpp:78-82) -- */
 int btlbf_kind(const btlbf_filter* f);
+unsigned btlbf_counter_bytes(const btlbf_filter* f); /* sizeof(T): 0 for a bit filter, else 1 / 2 / 4 / 8 */
 uint64_t btlbf_size(const btlbf_filter* f);        /* getFilterSize() bits / size() counters (global) */
 uint64_t btlbf_size_bytes(const btlbf_filter* f);  /* sizeInBytes() (global) */
 uint64_t btlbf_local_bytes(const btlbf_filter* f); /* bytes held by this object (== size_bytes unless a shard) */
@@ -189,7 +208,8 @@ int btlbf_download(const btlbf_filter* f, void* host_dst, uint64_t offset, uint6
  * array per batch).  AUTO picks PARTITIONED when the batch is large relative to the filter.  The
  * filter bytes are identical either way (bit OR is order-free).  scratch_bytes caps the scratch
  * allocation (0 = up to 80 % of the free HBM).  Default: BTLBF_INSERT_AUTO, or the environment
- * variable BTLBF_INSERT_MODE=direct|partitioned. */
+ * variable BTLBF_INSERT_MODE=direct|partitioned.  A wide counting filter accepts AUTO and DIRECT (AUTO means direct),
+ * returns EINVAL for PARTITIONED, and ignores the environment variable; the same holds for the query mode. */
 enum { BTLBF_INSERT_AUTO = 0, BTLBF_INSERT_DIRECT = 1, BTLBF_INSERT_PARTITIONED = 2 };
 int btlbf_set_insert_mode(btlbf_filter* f, int mode, uint64_t scratch_bytes);
 /* Same choice for btlbf_contains_seqs on a bit filter.  PARTITIONED tests the partitioned positions
@@ -258,6 +278,12 @@ int btlbf_insert_and_check_seqs(btlbf_filter* f, const char* seq, uint64_t len,
  * clean window, 0 for unclean windows and for the positions past a sequence's last window */
 int btlbf_min_count_seqs(btlbf_filter* f, const char* seq, uint64_t len, const btlbf_layout* layout,
                          uint8_t* min_out, uint64_t* valid_bits, int mem, void* stream);
+/* The same for every counter width: min_out holds len elements of btlbf_counter_bytes(f) bytes each (uint16_t,
+ * uint32_t or uint64_t for the wide kinds; BTLBF_COUNTING8: uint8_t, and the call equals the one above).  The byte
+ * forms above (btlbf_min_count_seqs, btlbf_min_count_hashes) return EINVAL on a wide filter with nothing written: the
+ * minimum would not fit the caller's bytes. */
+int btlbf_min_count_seqs_wide(btlbf_filter* f, const char* seq, uint64_t len, const btlbf_layout* layout,
+                              void* min_out, uint64_t* valid_bits, int mem, void* stream);
 
 /* ---- precomputed hashes: n k-mers x hash_num uint64_t, row-major ------------------------------
  * insert(const uint64_t[]) BloomFilter.hpp:185; contains(const uint64_t[]) :252;
@@ -270,6 +296,9 @@ int btlbf_insert_and_check_hashes(btlbf_filter* f, const uint64_t* hashes, uint6
                                   int order, int mem, void* stream);
 int btlbf_min_count_hashes(btlbf_filter* f, const uint64_t* hashes, uint64_t n, uint8_t* min_out,
                            int mem, void* stream);
+/* min_out: n elements of btlbf_counter_bytes(f) bytes each (see btlbf_min_count_seqs_wide) */
+int btlbf_min_count_hashes_wide(btlbf_filter* f, const uint64_t* hashes, uint64_t n, void* min_out, int mem,
+                                void* stream);
 
 /* ---- raw k-mers: KmerBloomFilter::insert(const char*) / contains(const char*) --------------------
  * (KmerBloomFilter.hpp:47-74 -> NTC64(kmerSeq, k) vendor/nthash.hpp:394-439,460-465 + NTE64 :537-542)
@@ -318,7 +347,7 @@ int btlbf_digest(btlbf_filter* f, uint64_t* out2);
 /* Position-wise comparison of two filters of the same kind, size (and shard range) on one device, without
  * leaving HBM -- what a caller of the reference does with two filter bodies and memcmp.  Bit filters:
  * out3 = {bits that differ, bits set only in a, bits set only in b}; counting filters: {counters that
- * differ, counters with a > b, counters with a < b}.  Synchronises the device. */
+ * differ, counters with a > b, counters with a < b}, per counter of the filter's width.  Synchronises the device. */
 int btlbf_compare(btlbf_filter* a, btlbf_filter* b, uint64_t* out3);
 
 /* ---- rank structure over a bit filter (miBF stage 2) ------------------------------------
@@ -530,7 +559,9 @@ int btlbf_mibf_classify_tally(const btlbf_mibf_hit* hits, const uint32_t* n_hits
  *   NULL) is the usual per-window bitmap.
  * insert_positions / test_positions act on local positions of this shard (test: one byte 0/1 each).
  * and_answers: origin side of a sharded query -- answers[i] belongs to probe tags[i]; a 0 answer
- *   clears the bit of window tags[i]/hash_num in hit_bits (which starts as a copy of valid_bits). */
+ *   clears the bit of window tags[i]/hash_num in hit_bits (which starts as a copy of valid_bits).
+ * positions_seqs, insert_positions, test_positions and every btlbf_route_* / btlbf_apply_* / btlbf_resolve_seqs /
+ * btlbf_owner_scratch_bytes call below: EINVAL before any HIP call for a wide counting filter. */
 int btlbf_positions_seqs(btlbf_filter* f, const char* seq, uint64_t len, const btlbf_layout* layout,
                          unsigned n_shards, uint64_t* buckets, uint64_t* tags, uint64_t bucket_cap,
                          uint64_t* bucket_counts, uint64_t* valid_bits, void* stream);
@@ -619,7 +650,7 @@ int btlbf_synth_reads(char* dev_out, uint64_t seed, uint64_t first_read, uint64_
 /* bare random-access ceilings on the filter's own array (SURVEY.md 8d "measured ceiling"):
  * kind 0 = independent 4-byte loads, 1 = 4-byte atomicOr (sets bits: clear the filter afterwards),
  * at uniformly random 64-byte-aligned offsets; about n_access accesses, the exact number is
- * returned in *n_done; *seconds = kernel time from HIP events */
+ * returned in *n_done; *seconds = kernel time from HIP events.  Wide counting filters: EINVAL. */
 int btlbf_microbench(btlbf_filter* f, int kind, uint64_t n_access, uint64_t* n_done, double* seconds);
 
 /* per-sequence totals of the per-window bitmaps that btlbf_contains_seqs / btlbf_insert_and_check_seqs

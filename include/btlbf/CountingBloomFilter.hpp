@@ -1,5 +1,6 @@
 // include/btlbf/CountingBloomFilter.hpp -- drop-in for the reference's `CountingBloomFilter<T>`
-// (/root/reference/CountingBloomFilter.hpp:26-111) with T = uint8_t, counters resident in HBM.
+// (/root/reference/CountingBloomFilter.hpp:26-111) with T = uint8_t, uint16_t, uint32_t or uint64_t, counters resident
+// in HBM.  The kind of the C ABI follows sizeof(T) (BTLBF_COUNTING8 / 16 / 32 / 64); size() = sizeInBytes() / sizeof(T).
 //
 // Same constructors and method names; `U` is any indexable holder of m_hashNum hash values, as in
 // the reference.  Per-k-mer calls apply in call order (BTLBF_ORDER_SERIAL on one row), so a
@@ -8,7 +9,8 @@
 // Threads: per-k-mer calls may come from many threads at once, as in the reference
 // (CountingBloomFilter.hpp:117-132); they are serialised by the filter's lock inside the C ABI.
 // Not reproduced: loadFilter's resize to sizeInBytes *elements* (CountingBloomFilter.hpp:275), an
-// over-allocation that only matters for T wider than a byte.
+// over-allocation that only matters for T wider than a byte.  Where the reference would silently misread a file whose
+// header does not fit T (BloomFilterSize * sizeof(T) != BloomFilterSizeInBytes), loading fails here.
 #ifndef BTLBF_COUNTINGBLOOMFILTER_HPP
 #define BTLBF_COUNTINGBLOOMFILTER_HPP
 #include "detail.hpp"
@@ -22,13 +24,18 @@
 template<typename T>
 class CountingBloomFilter
 {
-	static_assert(sizeof(T) == 1, "the MI355X engine implements 8-bit counters (uint8_t)");
+	static_assert(sizeof(T) == 1 || sizeof(T) == 2 || sizeof(T) == 4 || sizeof(T) == 8,
+	              "the MI355X engine implements 8-, 16-, 32- and 64-bit counters");
+	static constexpr int kKind = sizeof(T) == 1   ? BTLBF_COUNTING8
+	                             : sizeof(T) == 2 ? BTLBF_COUNTING16
+	                             : sizeof(T) == 4 ? BTLBF_COUNTING32
+	                                              : BTLBF_COUNTING64;
 
   public:
 	CountingBloomFilter() = default;
 	CountingBloomFilter(size_t sizeInBytes, unsigned hashNum, unsigned kmerSize, unsigned countThreshold)
 	{
-		btlbf_shim::check(btlbf_create(&m_f, BTLBF_COUNTING8, sizeInBytes, hashNum, kmerSize, countThreshold,
+		btlbf_shim::check(btlbf_create(&m_f, kKind, sizeInBytes, hashNum, kmerSize, countThreshold,
 		                               btlbf_shim::default_device()));
 	}
 	CountingBloomFilter(const std::string& path, unsigned countThreshold)
@@ -42,17 +49,22 @@ class CountingBloomFilter
 
 	T operator[](size_t i)
 	{
-		uint8_t v = 0;
-		btlbf_shim::check(btlbf_download(m_f, &v, i, 1));
-		return (T)v;
+		T v = 0;
+		btlbf_shim::check(btlbf_download(m_f, &v, i * sizeof(T), sizeof(T)));
+		return v;
 	}
 
 	template<typename U>
 	T minCount(const U& hashes) const // CountingBloomFilter.hpp:53-64
 	{
-		uint8_t v = 0;
-		btlbf_shim::check(btlbf_min_count_hashes(m_f, row(hashes), 1, &v, BTLBF_HOST, nullptr));
-		return (T)v;
+		if (sizeof(T) == 1) {
+			uint8_t v = 0;
+			btlbf_shim::check(btlbf_min_count_hashes(m_f, row(hashes), 1, &v, BTLBF_HOST, nullptr));
+			return (T)v;
+		}
+		T w = 0; // the full-width minimum
+		btlbf_shim::check(btlbf_min_count_hashes_wide(m_f, row(hashes), 1, &w, BTLBF_HOST, nullptr));
+		return w;
 	}
 	template<typename U>
 	bool contains(const U& hashes) const // :190-196
@@ -133,7 +145,7 @@ class CountingBloomFilter
 	{
 		btlbf_destroy(m_f);
 		m_f = nullptr;
-		btlbf_shim::check(btlbf_load(&m_f, BTLBF_COUNTING8, path.c_str(), m_threshold, btlbf_shim::default_device()));
+		btlbf_shim::check(btlbf_load(&m_f, kKind, path.c_str(), m_threshold, btlbf_shim::default_device()));
 	}
 	// loadHeader(std::istream&), CountingBloomFilter.hpp:84,282-330: the header lines up to "[HeaderEnd]" -> a zeroed
 	// filter of that geometry; the stream is left at the body (loadBody)
@@ -147,7 +159,7 @@ class CountingBloomFilter
 		}
 		btlbf_destroy(m_f);
 		m_f = nullptr;
-		btlbf_shim::check(btlbf_create_from_header(&m_f, BTLBF_COUNTING8, text.data(), text.size(), m_threshold,
+		btlbf_shim::check(btlbf_create_from_header(&m_f, kKind, text.data(), text.size(), m_threshold,
 		                                           btlbf_shim::default_device()));
 	}
 	void loadBody(std::istream& file)
