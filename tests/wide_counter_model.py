@@ -104,6 +104,18 @@ def check_increment_all(after, expect_after):
     _none(after != expect_after, "A1", "counter %d is %d, incrementAll gives %d", after, expect_after)
 
 
+def saturating_add(before, add, mx):
+    """before + add per counter, cut at `mx` -> uint64 array (exact for 64 bits too: the addend is cut to the room
+    below `mx` before it is added)"""
+    b = np.asarray(before, np.uint64)
+    return b + np.minimum(np.asarray(add, np.uint64), np.uint64(mx) - b)
+
+
+def increment_all_exact(before, pos, mx):
+    """incrementAll of the windows `pos` on `before`, order-free: saturating + (number of probes) per counter"""
+    return saturating_add(before, np.bincount(np.asarray(pos, np.int64).ravel(), minlength=len(before)), mx)
+
+
 def check_increment_min(before, after, upper, pos, mx):
     """M1-M4 for counters of maximum `mx`.  `upper`: incrementAll of the same windows on a copy of `before`."""
     before, after, upper = (np.asarray(x, np.uint64) for x in (before, after, upper))
