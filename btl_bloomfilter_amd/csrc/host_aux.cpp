@@ -389,6 +389,7 @@ extern "C" int btlbf_microbench(btlbf_filter* f, int kind, uint64_t n_access, ui
 	}
 	DeviceGuard g(f->device);
 	MATERIALIZE(f, nullptr);
+	HIP_TRY(hipDeviceSynchronize()); // DEVICE-mode calls may have run on non-blocking user streams
 	hipEvent_t e0, e1;
 	HIP_TRY(hipEventCreate(&e0));
 	HIP_TRY(hipEventCreate(&e1));

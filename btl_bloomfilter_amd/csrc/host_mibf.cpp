@@ -149,9 +149,12 @@ int mibf_prepare(MibfCall& c, const char* seq, uint64_t len, const btlbf_layout*
 	if (layout->starts) {
 		q.n_seqs = layout->n_seqs;
 		q.starts.resize(q.n_seqs + 1);
-		if (mem == BTLBF_DEVICE)
-			HIP_TRY(hipMemcpy(q.starts.data(), layout->starts, (q.n_seqs + 1) * 8, hipMemcpyDeviceToHost));
-		else
+		if (mem == BTLBF_DEVICE) {
+			// in the order of `s`: the caller's stream may still be producing the offsets (btlbf_interleave_mates on `s`
+			// writes them and returns), and a non-blocking stream is not waited for by a copy on the NULL stream
+			HIP_TRY(hipMemcpyAsync(q.starts.data(), layout->starts, (q.n_seqs + 1) * 8, hipMemcpyDeviceToHost, s));
+			HIP_TRY(hipStreamSynchronize(s));
+		} else
 			memcpy(q.starts.data(), layout->starts, (q.n_seqs + 1) * 8);
 		if (q.starts[0] != 0 || q.starts[q.n_seqs] != len)
 			return fail(BTLBF_EINVAL, "starts[0] must be 0 and starts[n_seqs] must equal len");

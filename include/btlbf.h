@@ -18,6 +18,22 @@
  *  - `stream` is a hipStream_t passed as void* (NULL = the default stream; BTLBF_STREAM_PER_THREAD = HIP's
  *    per-thread default stream, which lets BTLBF_HOST calls of different host threads overlap).  Work on one
  *    filter is ordered by the stream; BTLBF_HOST calls synchronise before returning.
+ *  - streams: a BTLBF_DEVICE call reads ALL of its inputs and writes ALL of its outputs in the order of `stream` --
+ *    the sequence bytes, `starts`, ids, hash rows and raw k-mers, the probability and minimum-count tables of the
+ *    classify calls and the running totals a call adds to.  Inputs that work queued earlier on that stream produces
+ *    need no host synchronisation (btlbf_interleave_mates on a stream and btlbf_mibf_classify_pairs of its buffer
+ *    and offsets on the same stream, with nothing in between), and work queued on the stream after the call has
+ *    returned sees its outputs and its changes to the filter.  The stream may be a non-blocking one, which the
+ *    NULL stream does not wait for.  Where the host has to look at an input (the miBF calls cut their batches on
+ *    `starts`) or at a result (counts the call returns by value), the call waits for `stream` itself; a DEVICE
+ *    call may therefore return before or after its work has run, and the caller assumes neither.  Using one filter
+ *    from two streams without an event between them is the caller's race.  The calls whose results are
+ *    host-visible and that take no stream wait for ALL streams of the device before they look at the array:
+ *    btlbf_download, btlbf_upload, btlbf_store / btlbf_store_shard, the judges (btlbf_popcount,
+ *    btlbf_filtered_popcount, btlbf_digest, btlbf_compare), btlbf_rank_create, btlbf_mibf_create and
+ *    btlbf_mibf_load; asynchronous DEVICE calls on any stream may precede them without a synchronisation by the
+ *    caller.  tests/test_gpu_stream_order.py holds the calls to this with inputs that are still in flight on a
+ *    non-blocking stream when the call is issued.
  *  - threads: every entry point that takes a filter holds the filter's internal lock for its whole duration
  *    (a filter keeps device scratch between calls), so ONE filter may be driven from many host threads -- the
  *    calls are serialised, the parallelism is inside each batch call -- and different filters run
