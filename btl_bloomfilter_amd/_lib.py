@@ -18,6 +18,8 @@ ORDER_PARALLEL, ORDER_SERIAL = 0, 1
 OK, EINVAL, ENOMEM, EIO, EFORMAT, EHIP = range(6)
 INSERT_AUTO, INSERT_DIRECT, INSERT_PARTITIONED = 0, 1, 2
 FASTX_LINES, FASTX_PAGEABLE, FASTX_WHOLE, CLASSIFY_INTERLEAVED = 1, 2, 4, 1 << 8
+MIBF_ID_PER_FILE, MIBF_ID_PER_RECORD = 0, 1
+MIBF_SAT_NONE, MIBF_SAT_SERIAL, MIBF_SAT_PARALLEL = 0, 1, 2
 PROF_SLOTS = 10
 PROF_NAMES = ["insert_direct", "query_direct", "insert_hash", "insert_split", "insert_apply", "query_hash",
               "query_split", "query_test", "query_resolve", "other"]
@@ -39,6 +41,24 @@ class FastxStats(C.Structure):
 class MibfClassifyParams(C.Structure):
     _fields_ = [("extra_count", C.c_double), ("extra_frame_limit", C.c_uint32), ("max_miss", C.c_uint32),
                 ("min_count", C.c_uint32), ("best_hit_agree", C.c_uint32), ("max_results", C.c_uint32)]
+
+
+class MibfBuildParams(C.Structure):
+    _fields_ = [("kmer_size", C.c_uint), ("hash_num", C.c_uint), ("seeds", C.POINTER(C.c_char_p)), ("n_seeds", C.c_uint),
+                ("id_bytes", C.c_uint), ("bits", C.c_uint64), ("expected_entries", C.c_uint64), ("occupancy", C.c_double),
+                ("id_mode", C.c_int), ("first_id", C.c_uint32), ("saturation", C.c_int), ("fastx_flags", C.c_uint32),
+                ("batch_bytes", C.c_uint64), ("scratch_bytes", C.c_uint64), ("device", C.c_int)]
+
+
+class MibfBuildReport(C.Structure):
+    _fields_ = [("entries", C.c_uint64), ("bits", C.c_uint64), ("pop", C.c_uint64), ("n_records", C.c_uint64),
+                ("n_ids", C.c_uint64), ("longest_record", C.c_uint64), ("n_bases", C.c_uint64), ("windows", C.c_uint64),
+                ("clean_windows", C.c_uint64), ("sat_counts4", C.c_uint64 * 4), ("batches", C.c_uint64 * 4),
+                ("seconds", C.c_double * 4), ("seconds_parse", C.c_double * 4), ("seconds_total", C.c_double)]
+
+    def as_dict(self):
+        return {k: (list(getattr(self, k)) if hasattr(getattr(self, k), "__len__") else getattr(self, k))
+                for k, _ in self._fields_}
 
 
 class BtlbfError(RuntimeError):
@@ -125,6 +145,11 @@ _PROTOS = {
     "btlbf_mibf_classify_fastx_close": (None, [_P]),
     "btlbf_mibf_classify_fastx": (C.c_int, [_P, C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(MibfClassifyParams), _P, _P,
                                             C.c_uint64, C.c_uint64, _P, _P, _P, C.POINTER(FastxStats)]),
+    "btlbf_mibf_build_fastx": (C.c_int, [C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_char_p), C.c_uint,
+                                         C.POINTER(MibfBuildParams), C.POINTER(MibfBuildReport), C.POINTER(C.c_uint64)]),
+    "btlbf_mibf_optimal_size": (C.c_uint64, [C.c_uint64, C.c_uint, C.c_double]),
+    "btlbf_count_windows_seqs": (C.c_int, [C.c_uint, _P, C.c_uint64, C.POINTER(Layout), _P, C.c_int, C.c_int, _P]),
+    "btlbf_count_windows_fastx": (C.c_int, [C.c_char_p, C.c_uint, C.c_uint32, C.c_uint64, C.c_int, C.POINTER(FastxStats)]),
     "btlbf_mibf_id_counts": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "btlbf_mibf_download": (C.c_int, [_P, _P]),
     "btlbf_mibf_upload": (C.c_int, [_P, _P]),

@@ -416,7 +416,7 @@ extern "C" int btlbf_mibf_saturate_seqs(btlbf_mibf* m, const char* seq, uint64_t
 	} else if (len) {
 		// decisions against the snapshot: mutations (rank, window) 16 bytes + 16 more for their sort, saturated ranks 8
 		// bytes each; half of the budget each
-		const uint64_t cap_mut = budget / 2 / 40, cap_sat = budget / 2 / 8;
+		const uint64_t cap_mut = mibf_parallel_cap_mut(budget), cap_sat = mibf_parallel_cap_sat(budget);
 		DevBuf kin, vin, sat, cnt;
 		if (kin.alloc(cap_mut * 8) || vin.alloc(cap_mut * 8) || sat.alloc(cap_sat * 8) || cnt.alloc(16)) {
 			(void)hipGetLastError();

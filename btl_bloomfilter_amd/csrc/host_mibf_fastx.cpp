@@ -13,6 +13,7 @@
 #include "../../include/btlbf.h"
 #include "internal.hpp"
 #include "host_internal.hpp"
+#include "fastx_side.hpp"
 #include "mibf_zip.hpp"
 
 #include <algorithm>
@@ -28,16 +29,6 @@
 #include <vector>
 
 using namespace btlbf;
-
-namespace {
-
-double now_s()
-{
-	using namespace std::chrono;
-	return duration<double>(steady_clock::now().time_since_epoch()).count();
-}
-
-} // namespace
 
 extern "C" int btlbf_interleave_mates(const char* seq1, const uint64_t* starts1, const char* seq2, const uint64_t* starts2,
                                       uint64_t n_pairs, char* out, uint64_t* out_starts, int mem, int device, void* stream)
@@ -104,95 +95,8 @@ extern "C" int btlbf_mibf_classify_tally(const btlbf_mibf_hit* hits, const uint3
 }
 
 // -------------------------------------------------------------------------------------------------
-// the file classifier
+// the file classifier (a file and its parser thread: Side, fastx_side.hpp)
 // -------------------------------------------------------------------------------------------------
-namespace {
-
-struct HostBatch {
-	const char* bases = nullptr;
-	const uint64_t* starts = nullptr;
-	uint64_t nb = 0, ns = 0; // ns == 0: end of input
-};
-
-// one file: its sequential parser on a thread of its own, at most two batches ahead of the consumer (the parser's two
-// buffers: one batch is handed back, by release(), before the parser may overwrite it)
-struct Side {
-	btlbf_fastx* r = nullptr;
-	std::thread th;
-	std::mutex mu;
-	std::condition_variable cv;
-	std::deque<HostBatch> q;
-	int credits = 2;
-	bool abort = false;
-	int rc = BTLBF_OK;
-	std::string err;
-	double seconds_parse = 0;
-	bool holding = false; // the consumer has a batch of this side
-
-	void run()
-	{
-		for (;;) {
-			{
-				std::unique_lock<std::mutex> lk(mu);
-				cv.wait(lk, [&] { return credits > 0 || abort; });
-				if (abort)
-					return;
-				--credits;
-			}
-			HostBatch b;
-			const double t0 = now_s();
-			const int e = btlbf_fastx_next(r, &b.bases, &b.nb, &b.starts, &b.ns);
-			{
-				std::lock_guard<std::mutex> lk(mu);
-				seconds_parse += now_s() - t0;
-				if (e) {
-					rc = e;
-					err = btlbf_last_error();
-					b = HostBatch();
-				}
-				q.push_back(b);
-			}
-			cv.notify_all();
-			if (e || b.ns == 0)
-				return;
-		}
-	}
-	// the next batch (ns == 0 at the end of input, and from then on); the one taken before goes back to the parser
-	int take(HostBatch* out)
-	{
-		std::unique_lock<std::mutex> lk(mu);
-		if (holding) {
-			holding = false;
-			++credits;
-			cv.notify_all();
-		}
-		cv.wait(lk, [&] { return !q.empty(); });
-		*out = q.front();
-		if (rc && out->ns == 0)
-			return btlbf_set_error(rc, "%s", err.c_str());
-		if (out->ns) {
-			q.pop_front();
-			holding = true;
-		}
-		return BTLBF_OK;
-	}
-	void stop()
-	{
-		{
-			std::lock_guard<std::mutex> lk(mu);
-			abort = true;
-		}
-		cv.notify_all();
-		if (th.joinable())
-			th.join();
-		if (r)
-			btlbf_fastx_close(r);
-		r = nullptr;
-	}
-};
-
-} // namespace
-
 struct btlbf_mibf_fastx {
 	btlbf_mibf* m = nullptr;
 	int device = 0;

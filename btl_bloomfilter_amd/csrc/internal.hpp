@@ -409,6 +409,13 @@ hipError_t launch_mibf_tally(const void* hits, const uint32_t* n_hits, const uin
                              const uint32_t* eval_count, uint64_t n_rows, uint32_t max_results, uint64_t n_ids,
                              unsigned long long* best, unsigned long long* any, unsigned long long* totals, hipStream_t s);
 
+// the miBF builder's device helpers (mibf_build_kernels.hip).  count_windows: out2 += {windows, clean windows} of the
+// sequences of seq[0, len) (the caller zeroes out2); fill_ids: ids[i] = first + i * step (step 1: an id per record,
+// step 0: the file's id)
+hipError_t launch_count_windows(const uint8_t* seq, uint64_t len, const LayoutParams& lay, uint32_t k,
+                                unsigned long long* out2, hipStream_t s);
+hipError_t launch_mibf_fill_ids(uint32_t* ids, uint64_t n, uint32_t first, uint32_t step, hipStream_t s);
+
 // counting filters with 16-, 32- and 64-bit counters (wide_counter_kernels.hip; `bytes` = 2, 4 or 8, the array holds
 // mod.size counters of that width).  Direct path only: one fused launch per sequence call, whole filters, no shards.
 enum WideSeqOp : int { W_QUERY = 0, W_INC_ALL = 1, W_INC_MIN = 2 };

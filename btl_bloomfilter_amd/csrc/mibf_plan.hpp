@@ -105,6 +105,36 @@ inline MibfPlan mibf_plan_serial(const MibfSeqs& q, uint64_t budget, uint32_t h)
 {
 	return mibf_plan(q, std::max<uint64_t>(1, budget / (8ull * h + 1)), ~0ull, mibf_cost_bytes);
 }
+// parallel saturation decides a whole batch against one snapshot, so it is not cut: its two lists take half of the budget
+// each -- a mutation 40 bytes ((rank, window) and as much for their sort, as an insert's hash value), a saturated rank 8.
+inline uint64_t mibf_parallel_cap_mut(uint64_t budget) { return budget / 2 / 40; }
+inline uint64_t mibf_parallel_cap_sat(uint64_t budget) { return budget / 2 / 8; }
+// the windows a batch of whole records of `bytes` bytes can hold: one record of all of them
+inline uint64_t mibf_batch_windows(uint64_t bytes, uint32_t k) { return bytes >= k ? bytes - k + 1 : 0; }
+// the worst case of a batch of `windows` windows fits: every window a mutation (one entry), or every window a saturation
+// (h ranks)
+inline bool mibf_parallel_fits(uint64_t windows, uint32_t h, uint64_t budget)
+{
+	return windows <= mibf_parallel_cap_mut(budget) && windows <= mibf_parallel_cap_sat(budget) / h;
+}
+// ... and the smallest budget under which it does (~0 where that is beyond 64 bits)
+inline uint64_t mibf_parallel_budget(uint64_t windows, uint32_t h)
+{
+	const uint64_t per = std::max<uint64_t>(80, 16ull * h);
+	return windows > ~0ull / per ? ~0ull : windows * per;
+}
+// the longest record one insert batch (serial: one serial saturation batch) holds, and the smallest budget that holds
+// `bytes` >= 2 (a batch always has room for one byte): the planners above, read backwards
+inline uint64_t mibf_record_room(uint64_t budget, uint32_t h, bool serial)
+{
+	return std::max<uint64_t>(1, budget / (serial ? 8ull * h + 1 : 40ull * h));
+}
+inline uint64_t mibf_record_budget(uint64_t bytes, uint32_t h, bool serial)
+{
+	const uint64_t per = serial ? 8ull * h + 1 : 40ull * h;
+	return bytes > ~0ull / per ? ~0ull : bytes * per;
+}
+
 // classify: per byte h values, the hit mask and two bitmap bits; per sequence whose table does not fit LDS, the table
 inline MibfPlan mibf_plan_classify(const MibfSeqs& q, uint64_t budget, uint32_t k, uint32_t h, uint32_t id_bytes,
                                    uint64_t n_ids)

@@ -646,6 +646,30 @@ def count_per_seq(hit_bits, valid_bits, n_bytes, k, starts=None, read_len=0, dev
     return hits, valid
 
 
+def countWindows(seq, k, starts=None, read_len=0, device=0, stream=None):
+    """(windows, clean windows) of the sequences of a buffer (btlbf_count_windows_seqs): a window is k bytes inside one
+    sequence, clean when the hash kernels accept every byte of it.  No hashing; host or device memory."""
+    b = _Buf(seq)
+    lay, keep = _layout(starts, read_len, b.mem)
+    out, optr = _out(b, 2, np.uint64)
+    dev = (b.keep.device.index or 0) if b.mem == DEVICE else device
+    check(_lib.load().btlbf_count_windows_seqs(int(k), b.ptr, b.nbytes, C.byref(lay) if lay else None, optr, b.mem, dev,
+                                                _stream_ptr(stream, b.keep)))
+    if b.mem == DEVICE:
+        out = out.cpu().numpy()
+    return int(out[0]), int(out[1])
+
+
+def countWindowsFile(path, k, per_line=False, batch_bytes=0, whole=False, device=0):
+    """countWindows over a FASTA / FASTQ file (btlbf_count_windows_fastx) -> the call's statistics: n_windows = clean
+    windows, n_hits = windows, n_records, n_bases, n_batches, seconds"""
+    st = _lib.FastxStats()
+    flags = (_lib.FASTX_LINES if per_line else 0) | (_lib.FASTX_WHOLE if whole else 0)
+    check(_lib.load().btlbf_count_windows_fastx(str(path).encode(), int(k), flags, int(batch_bytes), int(device),
+                                                 C.byref(st)))
+    return st.as_dict()
+
+
 def fastx_batches(path, k, per_line=False, batch_bytes=0, pageable=True, byte_range=None, fmt=None, whole=False):
     """Iterate over the parser's batches as (bases: bytes, starts: list[int]) -- the host-side reader
     behind insertFile (btlbf_fastx_open / btlbf_fastx_next); needs no GPU.  byte_range=(begin, end) with
@@ -770,6 +794,43 @@ class MIBloomFilter(_Owned):
         h = C.c_void_p()
         check(L.btlbf_mibf_load(C.byref(h), str(path).encode(), bloom._h, int(id_bytes)))
         return cls(None, id_bytes, _handle=h)
+
+    @staticmethod
+    def calcOptimalSize(entries, hash_num, occupancy):
+        """calcOptimalSize (MIBloomFilter.hpp:84-88): bits for `entries` entries of hash_num values at that occupancy"""
+        return _lib.load().btlbf_mibf_optimal_size(int(entries), int(hash_num), float(occupancy))
+
+    @classmethod
+    def buildFromFiles(cls, paths, k, h=None, seeds=None, id_bytes=2, bits=0, expected_entries=0, occupancy=0.5,
+                       ids="file", first_id=1, saturation="parallel", per_line=False, batch_bytes=0, scratch_bytes=0,
+                       device=0):
+        """A miBF from FASTA / FASTQ files (plain or gzip), stages 1-4 in one call (btlbf_mibf_build_fastx): size the bit
+        vector (bits, or calcOptimalSize of expected_entries, or of the files' clean windows, counted), insert every
+        sequence into the stage-1 filter, insertIDs, insertSaturation.  ids: "file" (file j gets first_id + j) or "record"
+        (record r over all files gets first_id + r); saturation: "parallel" (one parallel call per parser batch of
+        batch_bytes), "serial" (the reference's order) or None.  Whole records only: batch_bytes (0: 64 MiB) must hold the
+        longest.  -> (mibf, stage-1 BloomFilter, report dict; report["records_per_file"] lists the files' records)."""
+        L = _lib.load()
+        paths = [paths] if isinstance(paths, (str, bytes)) or hasattr(paths, "__fspath__") else list(paths)
+        enc = [p if isinstance(p, bytes) else str(p).encode() for p in paths]
+        parr = (C.c_char_p * max(len(enc), 1))(*enc)
+        sarr = None
+        if seeds is not None:
+            sarr = (C.c_char_p * len(seeds))(*[x.encode() if isinstance(x, str) else x for x in seeds])
+        par = _lib.MibfBuildParams(
+            int(k), int(h) if h is not None else (len(seeds) if seeds is not None else 0), sarr,
+            len(seeds) if seeds is not None else 0, int(id_bytes), int(bits), int(expected_entries), float(occupancy),
+            {"file": _lib.MIBF_ID_PER_FILE, "record": _lib.MIBF_ID_PER_RECORD}[ids], int(first_id),
+            {None: _lib.MIBF_SAT_NONE, "none": _lib.MIBF_SAT_NONE, "serial": _lib.MIBF_SAT_SERIAL,
+             "parallel": _lib.MIBF_SAT_PARALLEL}[saturation],
+            _lib.FASTX_LINES if per_line else 0, int(batch_bytes), int(scratch_bytes), int(device))
+        rep = _lib.MibfBuildReport()
+        per_file = (C.c_uint64 * max(len(enc), 1))()
+        hm, hf = C.c_void_p(), C.c_void_p()
+        check(L.btlbf_mibf_build_fastx(C.byref(hm), C.byref(hf), parr, len(enc), C.byref(par), C.byref(rep), per_file))
+        report = rep.as_dict()
+        report["records_per_file"] = list(per_file)[: len(enc)]
+        return cls(None, id_bytes, _handle=hm), BloomFilter(_handle=hf), report
 
     def getPop(self):
         return self._L.btlbf_mibf_size(self._h)

@@ -776,6 +776,92 @@ int btlbf_mibf_classify_fastx(btlbf_mibf* m, const char* path1, const char* path
                               const uint32_t* min_count_per_id, uint64_t n_ids, uint64_t batch_bytes, uint64_t* best,
                               uint64_t* any, uint64_t* totals6, btlbf_fastx_stats* stats);
 
+/* ---- miBF construction from FASTA / FASTQ files (stages 1-4) ------------------------------------------------
+ * What a caller of the reference's MIBFConstructSupport writes around insertBVColli / getEmptyMIBF / insertMIBF /
+ * insertSaturation: read the reference sequences, size the bit vector (calcOptimalSize, MIBloomFilter.hpp:84-88), give
+ * every sequence its id, run the passes in order.  mibf_build_fastx does that over files, in argument order, records in
+ * file order:
+ *   pass 0 (count)  : only when bits == 0 && expected_entries == 0: the clean windows of all files
+ *                     (count_windows_seqs per batch) are the entries the bit vector is sized for;
+ *   pass 1 (stage 1): a bit filter of `bits` bits (plain ntHash with hash_num values, or the spaced seeds with h2 = 1),
+ *                     every sequence inserted (insert_seqs per batch); it also counts the records and finds the longest;
+ *   stage 2         : mibf_create;
+ *   pass 2          : mibf_insert_ids_seqs per batch, with the ids made on the device;
+ *   pass 3          : mibf_saturate_seqs per batch, unless BTLBF_MIBF_SAT_NONE.
+ * Every pass reads the files again.  One sequential parser per file runs ahead on a thread of its own (the
+ * classifier's arrangement); a parser batch goes to one of two device slots on a copy stream, so that batch j + 1 is
+ * copied while the stage call of batch j, which plans on the host and synchronises the compute stream, runs.
+ * A sequence is what btlbf_fastx_open(path, flags | BTLBF_FASTX_WHOLE, k, batch_bytes) delivers (flags: BTLBF_FASTX_LINES,
+ * BTLBF_FASTX_PAGEABLE): whole records only -- batch_bytes (0 = 64 MiB) must hold the longest record, and a longer one is
+ * the parser's EINVAL, naming the record.  Wrapped FASTA lines are one sequence unless BTLBF_FASTX_LINES is set; a FASTQ
+ * record with an empty sequence line is a sequence (and, per record, takes an id); a FASTA record without sequence lines
+ * is not.  Record names are not delivered: there is no id-to-name table.  A batch never spans two files.
+ * ids: BTLBF_MIBF_ID_PER_FILE: every sequence of file j gets first_id + j; BTLBF_MIBF_ID_PER_RECORD: sequence r, counted
+ * over all files in order, gets first_id + r.
+ * The result, with S = all sequences in that order, with their ids:
+ *   E1  the stage-1 body is byte for byte that of btlbf_insert_seqs of S into an empty filter of that size, seeds and k;
+ *   E2  after pass 2, data and counts equal ONE btlbf_mibf_insert_ids_seqs call over S (its ascending-value rule makes
+ *       the result independent of batch cuts; a cut record would change the counts, hence whole records);
+ *   E3  SAT_SERIAL equals ONE BTLBF_ORDER_SERIAL call over S;
+ *   E4  SAT_PARALLEL equals one BTLBF_ORDER_PARALLEL call per parser batch, in order: the batches are those
+ *       btlbf_fastx_open(path, flags | BTLBF_FASTX_WHOLE, k, batch_bytes) / _next deliver for each file in turn, so the
+ *       result depends on batch_bytes; report->sat_counts4 sums the counts4 of those calls;
+ *   E5  bits == 0 gives btlbf_mibf_optimal_size(entries, hash_num, occupancy), entries being expected_entries or pass 0's
+ *       count: the reference's arithmetic, the same double operations in the same order.
+ * Checked at entry, before any HIP call and with nothing allocated: null or empty arguments; an unreadable path, any of
+ * them (EIO, naming it); id_bytes other than 2 / 4; first_id == 0; per file, first_id + n_paths - 1 at or above the
+ * saturation mask 1 << (8 * id_bytes - 1); an unknown id_mode or saturation; occupancy outside (0, 1) when bits == 0; a
+ * `bits` that is 0 after sizing or no multiple of 8; hash_num outside 1..8; kmer_size == 0; seeds whose count or length
+ * disagree with hash_num / kmer_size; for SAT_PARALLEL a batch_bytes whose worst case -- every window of a batch a
+ * mutation, every probe a saturation -- does not fit the shares the parallel call gives the two lists of scratch_bytes
+ * (0 = the default 2 GiB): ENOMEM, the message states the budget that would do (mibf_parallel_budget, csrc/mibf_plan.hpp).
+ * Checked at the end of pass 1, before stage 2: per record, the last id at or above the mask (EINVAL); the longest
+ * record beyond what one insert batch, or with SAT_SERIAL one serial saturation batch, holds under the budget (ENOMEM,
+ * stating the budget needed).  Read errors are EIO.  On any failure *out and *stage1_out are NULL and nothing is left
+ * allocated.  stage1_out may be NULL (the filter is then destroyed; store it with btlbf_store to load the miBF again);
+ * report and records_per_file[n_paths] are optional.
+ * mibf_optimal_size  : calcOptimalSize (MIBloomFilter.hpp:84-88), pure host arithmetic.
+ * count_windows_seqs : out2 = {windows, clean windows} of the sequences of a buffer (layout as btlbf_insert_seqs; NULL:
+ *                     one sequence).  A window is k bytes inside one sequence; it is clean when each of them is a base
+ *                     the hash kernels accept -- don't-care positions of spaced seeds included, so the count depends on
+ *                     k alone.  No hashing.  out2 lives in memory space mem; a DEVICE call returns with the work queued.
+ * count_windows_fastx: the same over a file; stats->n_windows = clean windows, n_hits = windows. */
+enum { BTLBF_MIBF_ID_PER_FILE = 0, BTLBF_MIBF_ID_PER_RECORD = 1 };
+enum { BTLBF_MIBF_SAT_NONE = 0, BTLBF_MIBF_SAT_SERIAL = 1, BTLBF_MIBF_SAT_PARALLEL = 2 };
+typedef struct btlbf_mibf_build_params {
+	unsigned kmer_size, hash_num; /* with seeds: hash_num == n_seeds */
+	const char* const* seeds;
+	unsigned n_seeds;
+	unsigned id_bytes; /* 2 | 4 */
+	uint64_t bits;             /* 0: btlbf_mibf_optimal_size(entries, hash_num, occupancy) */
+	uint64_t expected_entries; /* 0: counted (pass 0) */
+	double occupancy;
+	int id_mode;
+	uint32_t first_id;
+	int saturation;
+	uint32_t fastx_flags;
+	uint64_t batch_bytes, scratch_bytes;
+	int device;
+} btlbf_mibf_build_params;
+typedef struct btlbf_mibf_build_report {
+	uint64_t entries; /* what the bit vector was sized for; 0 when bits was given */
+	uint64_t bits, pop;
+	uint64_t n_records, n_ids; /* sequences over all files; ids assigned (n_paths or n_records) */
+	uint64_t longest_record, n_bases;
+	uint64_t windows, clean_windows; /* pass 0; 0 when it did not run */
+	uint64_t sat_counts4[4];         /* {clean windows, found, mutated, saturated} summed over pass 3's calls */
+	uint64_t batches[4];             /* per pass */
+	double seconds[4], seconds_parse[4];
+	double seconds_total;
+} btlbf_mibf_build_report;
+int btlbf_mibf_build_fastx(btlbf_mibf** out, btlbf_filter** stage1_out, const char* const* paths, unsigned n_paths,
+                           const btlbf_mibf_build_params* p, btlbf_mibf_build_report* report, uint64_t* records_per_file);
+uint64_t btlbf_mibf_optimal_size(uint64_t entries, unsigned hash_num, double occupancy);
+int btlbf_count_windows_seqs(unsigned kmer_size, const char* seq, uint64_t len, const btlbf_layout* layout, uint64_t* out2,
+                             int mem, int device, void* stream);
+int btlbf_count_windows_fastx(const char* path, unsigned kmer_size, uint32_t flags, uint64_t batch_bytes, int device,
+                              btlbf_fastx_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,8 @@
 //   * construction: from a stage-1 bit filter (MIBloomFilter(hashNum, k, bv, seeds), :122-147) or from a data file
 //     plus that filter (MIBloomFilter(path), :149-248; the bit vector is not read from a .sdsl file).
 //   * calcFrameProbs / calcProbSingleFrame as in the reference (the perFrameProb table of MIBFQuerySupport).
+//   * buildFromFiles: stages 1-4 from FASTA / FASTQ files in one call (btlbf_mibf_build_fastx), what a caller of
+//     MIBFConstructSupport writes by hand; calcOptimalSize with the reference's name and arithmetic.
 //   * batch members instead of per-k-mer iterators: insertIDs (insertMIBF), insertSaturation, query
 //     (getMatchSignature) over sequence buffers with a layout and one id per sequence.
 // Errors follow detail.hpp (message + exit(1), or std::runtime_error with BTLBF_SHIM_THROW).
@@ -16,6 +18,27 @@
 #include <vector>
 
 namespace btlbf {
+
+// buildFromFiles' arguments: btlbf_mibf_build_params with the seeds as strings (empty: plain ntHash with hashNum
+// values; otherwise one value per seed) and the id width taken from T
+// (MIBloomFilter<T>::BuildOptions / ::BuildReport for every T)
+struct MIBFBuildOptions
+{
+	unsigned kmerSize = 0, hashNum = 0;
+	std::vector<std::string> seeds;
+	uint64_t bits = 0, expectedEntries = 0;
+	double occupancy = 0.5;
+	bool idPerRecord = false;
+	uint32_t firstId = 1;
+	int saturation = BTLBF_MIBF_SAT_PARALLEL;
+	bool perLine = false;
+	uint64_t batchBytes = 0, scratchBytes = 0;
+	int device = 0;
+};
+struct MIBFBuildReport : btlbf_mibf_build_report
+{
+	std::vector<uint64_t> recordsPerFile;
+};
 
 template<typename T>
 class MIBloomFilter
@@ -31,6 +54,50 @@ class MIBloomFilter
 	MIBloomFilter(const std::string& filterFilePath, btlbf_filter* stage1)
 	{
 		btlbf_shim::check(btlbf_mibf_load(&m_m, filterFilePath.c_str(), stage1, sizeof(T)));
+	}
+
+	typedef MIBFBuildOptions BuildOptions;
+	typedef MIBFBuildReport BuildReport;
+
+	// calcOptimalSize (MIBloomFilter.hpp:84-88)
+	static size_t calcOptimalSize(size_t entries, unsigned hashNum, double occupancy)
+	{
+		return btlbf_mibf_optimal_size(entries, hashNum, occupancy);
+	}
+
+	// stages 1-4 over the files, in order (the contract is btlbf_mibf_build_fastx's); the caller owns the result and,
+	// when asked for, the stage-1 filter (store it with btlbf_store: the data file of store() does not hold the bits)
+	static MIBloomFilter<T>* buildFromFiles(const std::vector<std::string>& paths, const BuildOptions& o,
+	                                        BuildReport* report = nullptr, btlbf_filter** stage1 = nullptr)
+	{
+		std::vector<const char*> pp, sp;
+		for (size_t i = 0; i < paths.size(); ++i)
+			pp.push_back(paths[i].c_str());
+		for (size_t i = 0; i < o.seeds.size(); ++i)
+			sp.push_back(o.seeds[i].c_str());
+		btlbf_mibf_build_params p;
+		p.kmer_size = o.kmerSize;
+		p.hash_num = o.seeds.empty() ? o.hashNum : (unsigned)o.seeds.size();
+		p.seeds = sp.empty() ? nullptr : &sp[0];
+		p.n_seeds = (unsigned)sp.size();
+		p.id_bytes = sizeof(T);
+		p.bits = o.bits;
+		p.expected_entries = o.expectedEntries;
+		p.occupancy = o.occupancy;
+		p.id_mode = o.idPerRecord ? BTLBF_MIBF_ID_PER_RECORD : BTLBF_MIBF_ID_PER_FILE;
+		p.first_id = o.firstId;
+		p.saturation = o.saturation;
+		p.fastx_flags = o.perLine ? BTLBF_FASTX_LINES : 0;
+		p.batch_bytes = o.batchBytes;
+		p.scratch_bytes = o.scratchBytes;
+		p.device = o.device;
+		std::vector<uint64_t> perFile(paths.size() + 1, 0);
+		btlbf_mibf* m = nullptr;
+		btlbf_shim::check(btlbf_mibf_build_fastx(&m, stage1, pp.empty() ? nullptr : &pp[0], (unsigned)pp.size(), &p, report,
+		                                         &perFile[0]));
+		if (report)
+			report->recordsPerFile.assign(perFile.begin(), perFile.begin() + paths.size());
+		return new MIBloomFilter<T>(m);
 	}
 
 	~MIBloomFilter() { btlbf_mibf_destroy(m_m); }
@@ -126,6 +193,7 @@ class MIBloomFilter
 
   private:
 	btlbf_mibf* m_m = nullptr;
+	explicit MIBloomFilter(btlbf_mibf* m) : m_m(m) {}
 
 	std::vector<uint64_t> stats() const
 	{
