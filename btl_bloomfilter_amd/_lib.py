@@ -20,6 +20,7 @@ INSERT_AUTO, INSERT_DIRECT, INSERT_PARTITIONED = 0, 1, 2
 FASTX_LINES, FASTX_PAGEABLE, FASTX_WHOLE, CLASSIFY_INTERLEAVED = 1, 2, 4, 1 << 8
 MIBF_ID_PER_FILE, MIBF_ID_PER_RECORD = 0, 1
 MIBF_SAT_NONE, MIBF_SAT_SERIAL, MIBF_SAT_PARALLEL = 0, 1, 2
+SCREEN_MAX_FILTERS = 16
 PROF_SLOTS = 10
 PROF_NAMES = ["insert_direct", "query_direct", "insert_hash", "insert_split", "insert_apply", "query_hash",
               "query_split", "query_test", "query_resolve", "other"]
@@ -41,6 +42,10 @@ class FastxStats(C.Structure):
 class MibfClassifyParams(C.Structure):
     _fields_ = [("extra_count", C.c_double), ("extra_frame_limit", C.c_uint32), ("max_miss", C.c_uint32),
                 ("min_count", C.c_uint32), ("best_hit_agree", C.c_uint32), ("max_results", C.c_uint32)]
+
+
+class ScreenParams(C.Structure):
+    _fields_ = [("min_fraction", C.c_double), ("min_hits", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class MibfBuildParams(C.Structure):
@@ -204,6 +209,17 @@ _PROTOS = {
     "btlbf_fastx_close": (None, [_P]),
     "btlbf_insert_fastx": (C.c_int, [_P, C.c_char_p, C.c_uint32, C.c_uint64, C.POINTER(FastxStats)]),
     "btlbf_contains_fastx": (C.c_int, [_P, C.c_char_p, C.c_uint32, C.c_uint64, C.POINTER(FastxStats)]),
+    "btlbf_screen_seqs": (C.c_int, [_P, C.c_uint, _P, C.c_uint64, C.POINTER(Layout), C.POINTER(ScreenParams), _P, _P, _P,
+                                    C.c_int, _P]),
+    "btlbf_screen_tally": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint, _P, _P, _P, C.c_int, C.c_int, _P]),
+    "btlbf_screen_fastx_open": (C.c_int, [C.POINTER(_P), _P, C.c_uint, C.c_char_p, C.c_uint32, C.POINTER(ScreenParams),
+                                          C.c_uint64]),
+    "btlbf_screen_fastx_next": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(_P), C.POINTER(_P),
+                                          C.POINTER(_P)]),
+    "btlbf_screen_fastx_tally": (C.c_int, [_P, _P, _P, _P]),
+    "btlbf_screen_fastx_close": (None, [_P]),
+    "btlbf_screen_fastx": (C.c_int, [_P, C.c_uint, C.c_char_p, C.c_uint32, C.POINTER(ScreenParams), C.c_uint64, _P, _P, _P,
+                                     C.POINTER(FastxStats)]),
 }
 EXPORTS = sorted(_PROTOS)
 

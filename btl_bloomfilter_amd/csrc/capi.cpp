@@ -456,6 +456,8 @@ extern "C" int btlbf_destroy(btlbf_filter* f)
 		(void)hipEventDestroy(f->clear_ev);
 	if (f->zero_ev)
 		(void)hipEventDestroy(f->zero_ev);
+	if (f->screen_ev)
+		(void)hipEventDestroy(f->screen_ev);
 	(void)hipFree(f->d_data);
 	(void)hipFree(f->d_scalar);
 	(void)hipFree(f->d_pos_tab);
@@ -463,6 +465,7 @@ extern "C" int btlbf_destroy(btlbf_filter* f)
 	f->part.release();
 	f->split.release();
 	f->flags.release();
+	f->screen.release();
 	delete f;
 	return BTLBF_OK;
 }
@@ -488,6 +491,7 @@ extern "C" int btlbf_release_scratch(btlbf_filter* f)
 	f->part.release();
 	f->split.release();
 	f->flags.release();
+	f->screen.release();
 	dev_pool().drain(f->device); // parked staging buffers of HOST-mode calls (every user has synchronised)
 	return BTLBF_OK;
 }

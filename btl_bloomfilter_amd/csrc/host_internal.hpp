@@ -103,6 +103,11 @@ struct btlbf_filter {
 	btlbf::DevScratch part;
 	btlbf::DevScratch split; // split query: compacted reads + their bitmaps
 	btlbf::DevScratch flags; // split query: cold flags of the reads + their prefix sums (small)
+	btlbf::DevScratch screen; // read screen (host_screen.cpp): the per-window bitmaps of a btlbf_screen_seqs call
+	// ... which a BTLBF_DEVICE call leaves in use when it returns: screen_ev is recorded behind its last kernel, and the next
+	// call that takes the scratch (under this filter's lock, on whatever stream) makes its stream wait for it first
+	hipEvent_t screen_ev = nullptr;
+	bool screen_ev_pending = false;
 	uint64_t part_budget = 0; // 0 = derive from free HBM
 	// optional per-kernel timing with HIP events on the launch stream (btlbf_set_profiling)
 	bool profiling = false;

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "mibf_plan.hpp"
+#include "screen_plan.hpp"
 
 namespace btlbf {
 
@@ -432,5 +433,34 @@ hipError_t launch_wide_popcount(const void* data, uint64_t nbytes, int bytes, in
                                 unsigned long long* out, hipStream_t s);
 hipError_t launch_wide_compare(const void* a, const void* b, uint64_t nbytes, int bytes, unsigned long long* out3,
                                hipStream_t s);
+
+// the read screen (screen_kernels.hip): one pass over a sequence buffer probes up to kScreenMaxNF bit filters (whole
+// ones, same k / hash count / seeds: `hp` is any one's) with every window's hash values, computed once.  Filter j of the
+// launch writes the hit bitmap at hit_cols + j * col_bytes (byte view, as SeqArgs::hit_bits); valid_bits may be null.
+struct ScreenArgs {
+	const uint8_t* seq; // device
+	uint64_t len;
+	LayoutParams layout;
+	HashParams hp;
+	uint32_t nf;
+	const uint32_t* words[kScreenMaxNF];
+	ModParams mod[kScreenMaxNF];
+	uint8_t* hit_cols;
+	uint64_t col_bytes;
+	uint8_t* valid_bits;
+	uint64_t n_tiles, tiles_per_block;
+};
+hipError_t launch_screen(const ScreenArgs& a, hipStream_t s);
+// cols: n_filters hit bitmaps and then the valid bitmap, col_words 64-bit words apart -> hits[n_rows * n_filters],
+// valid[n_rows] (what btlbf_count_per_seq counts; a layout of neither offsets nor read_len: one row, the buffer)
+hipError_t launch_screen_reduce(const uint64_t* cols, uint64_t col_words, uint64_t len, const LayoutParams& lay,
+                                uint64_t n_rows, uint32_t k, uint32_t n_filters, uint32_t* hits, uint32_t* valid,
+                                hipStream_t s);
+hipError_t launch_screen_verdict(const uint32_t* hits, const uint32_t* valid, uint64_t n_rows, uint32_t n_filters,
+                                 double min_fraction, uint32_t min_hits, uint32_t* pass_bits, hipStream_t s);
+// adds into passed[n_filters], best[n_filters], totals4 and -- where given -- windows (the sum of valid)
+hipError_t launch_screen_tally(const uint32_t* hits, const uint32_t* valid, const uint32_t* pass_bits, uint64_t n_rows,
+                               uint32_t n_filters, unsigned long long* passed, unsigned long long* best,
+                               unsigned long long* totals4, unsigned long long* windows, hipStream_t s);
 
 } // namespace btlbf

@@ -933,6 +933,26 @@ __device__ __forceinline__ void seq_lane_windows(const uint8_t* tile, const SeqS
 	seq_lane_range<SPACED, KW, HS, 0, KW>(tile, sh, hp, spaced_lds, li0, st, f);
 }
 
+// The forward and reverse strand hash of each of a lane's KW windows, one window at a time: f(w, clean, fh, rh).  This is
+// the plain-ntHash walk above (start-up over the first window, then one roll per window) taken in pieces of one
+// window, whose state -- the two hashes included -- LaneState carries between the pieces.  The start-up takes the Horner
+// form (use_pos_tab = 0): it needs init_tab alone, whatever layout the positional table in LDS has.
+template <int W, int KW = kW, class F>
+__device__ __forceinline__ void seq_strand_walk(const uint8_t* tile, const SeqShared& sh, uint32_t k, uint64_t kms,
+                                                 uint32_t li0, LaneState& st, F&& f)
+{
+	HashParams hp; // what the plain walk reads: k, use_pos_tab, kms
+	hp.k = k;
+	hp.use_pos_tab = 0;
+	hp.kms = kms;
+	hp.n_seeds = 0;
+	bool ok = false;
+	seq_lane_range<false, KW, 0, W, W + 1>(tile, sh, hp, tile, li0, st, [&](int, bool o, const WinHash<false>&) { ok = o; });
+	f(W, ok, st.fh, st.rh);
+	if constexpr (W + 1 < KW)
+		seq_strand_walk<W + 1, KW>(tile, sh, k, kms, li0, st, f);
+}
+
 // advance "offset of the tile start inside its read" by one tile (uniform layout)
 __device__ __forceinline__ uint32_t seq_next_tile_off(uint32_t tile_off, uint32_t tile_step, uint32_t L)
 {

@@ -4,7 +4,7 @@
 //     built on seq_core.hpp exactly as seq_kernel is (seq_kernels.hip): 256 threads, 8 windows per lane, one byte of the
 //     per-window bitmaps per lane, the same `counts` reduction.  Ops: query (hit bit, optional full-width minimum),
 //     incrementAll, incrementMin.  With spaced seeds the h values of a window are produced and probed one at a time
-//     (wide_spaced_walk), so that no instantiation keeps a run-time-indexed array of them in scratch memory;
+//     (seq_core.hpp: seq_strand_walk), so that no instantiation keeps a run-time-indexed array of them in scratch memory;
 //   * hash-row kernels, one lane per row or one lane in all (strict order), as aux_kernels.hip has them for bytes;
 //   * reductions: non-zero counters, counters >= threshold, the three-way compare of two arrays.
 // The width is a template parameter everywhere (wide_counter.hpp); the hash count stays a run-time value.  Positions are
@@ -16,26 +16,6 @@ namespace btlbf {
 
 static constexpr int kWideThreads = 256;
 static constexpr int kWideTile = kWideThreads * kW;
-
-// The forward and reverse strand hash of each of a lane's kW windows, one window at a time: f(w, clean, fh, rh).  This is
-// seq_core.hpp's plain-ntHash walk (start-up over the first window, then one roll per window) taken in pieces of one
-// window, whose state -- the two hashes included -- LaneState carries between the pieces.  The start-up takes the Horner
-// form (use_pos_tab = 0): it needs init_tab alone, whatever layout the positional table in LDS has.
-template <int W, class F>
-__device__ __forceinline__ void wide_spaced_walk(const uint8_t* tile, const SeqShared& sh, uint32_t k, uint64_t kms,
-                                                 uint32_t li0, LaneState& st, F&& f)
-{
-	HashParams hp; // what the plain walk reads: k, use_pos_tab, kms
-	hp.k = k;
-	hp.use_pos_tab = 0;
-	hp.kms = kms;
-	hp.n_seeds = 0;
-	bool ok = false;
-	seq_lane_range<false, kW, 0, W, W + 1>(tile, sh, hp, tile, li0, st, [&](int, bool o, const WinHash<false>&) { ok = o; });
-	f(W, ok, st.fh, st.rh);
-	if constexpr (W + 1 < kW)
-		wide_spaced_walk<W + 1>(tile, sh, k, kms, li0, st, f);
-}
 
 template <int OP, int BYTES, bool POW2, bool SPACED>
 __global__ __launch_bounds__(kWideThreads) void wide_seq_kernel(const SeqArgs a)
@@ -115,7 +95,7 @@ __global__ __launch_bounds__(kWideThreads) void wide_seq_kernel(const SeqArgs a)
 			const uint16_t* dc_idx = reinterpret_cast<const uint16_t*>(spaced_lds + seq_pos_tab_bytes(a.hp));
 			const uint32_t n_seeds = a.hp.n_seeds, h2 = a.hp.h2;
 			LaneState st;
-			wide_spaced_walk<0>(tile, sh, k, a.hp.kms, li0, st, [&](int w, bool ok, uint64_t fh, uint64_t rh) {
+			seq_strand_walk<0>(tile, sh, k, a.hp.kms, li0, st, [&](int w, bool ok, uint64_t fh, uint64_t rh) {
 				window(w, ok, [&](auto&& g) {
 					for (uint32_t j = 0; j < n_seeds; ++j) {
 						uint64_t fs = fh, rs = rh;

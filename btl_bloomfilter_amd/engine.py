@@ -1073,3 +1073,113 @@ class _ClassifyFile(_Owned):
         check(self._L.btlbf_mibf_classify_fastx_tally(self._h, C.c_void_p(best.ctypes.data), C.c_void_p(any_.ctypes.data),
                                                       C.c_void_p(totals.ctypes.data)))
         return best[: self.n_ids], any_[: self.n_ids], totals
+
+
+# -- read screen (btlbf_screen_*): every read against several bit filters in one pass -----------------------------
+def _filter_handles(filters):
+    filters = list(filters)
+    arr = (C.c_void_p * max(len(filters), 1))(*[f._h for f in filters])
+    return filters, arr
+
+
+def screenSeqs(filters, seq, starts=None, read_len=0, min_fraction=0.0, min_hits=1, stream=None):
+    """The reads of a sequence buffer against every filter of `filters` (BloomFilter objects of one k, hash count and
+    seeds, up to 16) in one pass (btlbf_screen_seqs) -> (hits[n, F], valid[n], pass_bits[n]), uint32: valid[s] = the
+    clean windows of sequence s, hits[s, j] = those found in filters[j] -- what containsSeqs + count_per_seq give per
+    filter --, bit j of pass_bits[s] = valid > 0 and hits >= min_hits and hits >= min_fraction * valid.  Buffers as
+    containsSeqs takes them (host memory, or torch tensors on the GPU and then results as int32 tensors); neither
+    starts nor read_len: the buffer is one sequence."""
+    filters, arr = _filter_handles(filters)
+    b = _Buf(seq)
+    lay, keep = _layout(starts, read_len, b.mem)
+    n = lay.n_seqs if starts is not None else (b.nbytes // int(read_len) if read_len else 1)
+    nf = len(filters)
+    hits, p_hits = _out(b, (n, nf), np.uint32)
+    valid, p_valid = _out(b, n, np.uint32)
+    pb, p_pb = _out(b, n, np.uint32)
+    par = _lib.ScreenParams(float(min_fraction), int(min_hits), 0)
+    check(_lib.load().btlbf_screen_seqs(arr, nf, b.ptr, b.nbytes, C.byref(lay) if lay else None, C.byref(par), p_hits,
+                                         p_valid, p_pb, b.mem, _stream_ptr(stream, b.keep)))
+    return hits, valid, pb
+
+
+def screen_tally(hits, valid, pass_bits, passed=None, best=None, totals=None, device=0, stream=None):
+    """btlbf_screen_tally: adds the summary of screened rows to (passed[F], best[F], totals[4]) and returns them:
+    rows passing filter j; rows whose passing filter with the most hits is j (ties: the lowest j); {rows, rows passing
+    none, rows passing two or more, rows without a clean window}.  Host results with uint64 numpy totals, or device
+    results (screenSeqs' tensors) with int64 tensors; the totals are made, zeroed, where they are not given."""
+    b = _Buf(hits, np.uint32)
+    n_rows = len(valid)
+    nf = int(hits.shape[1])
+    outs = []
+    for x, n in ((passed, nf), (best, nf), (totals, 4)):
+        if x is None:
+            x, _ = _out(b, n, np.uint64)
+        outs.append(x)
+    args = [_Buf(x, np.uint32) for x in (valid, pass_bits)] + [_Buf(x, np.uint64) if b.mem == HOST else _Buf(x) for x in outs]
+    if any(a.mem != b.mem for a in args):
+        raise ValueError("screen_tally: all arrays live in one memory space")
+    for x, a in zip(outs, args[2:]):
+        if b.mem == HOST and a.keep is not x:
+            raise ValueError("screen_tally: the totals are contiguous uint64 arrays")
+    check(_lib.load().btlbf_screen_tally(b.ptr, args[0].ptr, args[1].ptr, n_rows, nf, args[2].ptr, args[3].ptr, args[4].ptr,
+                                          b.mem, (b.keep.device.index or 0) if b.mem == DEVICE else device,
+                                          _stream_ptr(stream, b.keep)))
+    return tuple(outs)
+
+
+def screenFile(filters, path, min_fraction=0.0, min_hits=1, batch_bytes=0, per_line=False, summary_only=False):
+    """screenSeqs over the records of one FASTA / FASTQ file (plain or gzip), in file order (btlbf_screen_fastx_*): an
+    iterator of (first_row, hits[n, F], valid[n], pass_bits[n]) per batch of at most batch_bytes bases (0: 64 MiB),
+    numpy arrays copied out of the library's buffers; its tally() gives the running summary, close() ends it early.
+    With summary_only=True no per-read result leaves the GPU and the call returns (passed[F], best[F], totals[4],
+    stats) as screen_tally defines them, stats being the call's statistics (n_windows = the sum of valid)."""
+    filters, arr = _filter_handles(filters)
+    par = _lib.ScreenParams(float(min_fraction), int(min_hits), 0)
+    flags = _lib.FASTX_LINES if per_line else 0
+    nf = len(filters)
+    if summary_only:
+        passed, best, totals = np.zeros(max(nf, 1), np.uint64), np.zeros(max(nf, 1), np.uint64), np.zeros(4, np.uint64)
+        st = _lib.FastxStats()
+        check(_lib.load().btlbf_screen_fastx(arr, nf, str(path).encode(), flags, C.byref(par), int(batch_bytes),
+                                              C.c_void_p(passed.ctypes.data), C.c_void_p(best.ctypes.data),
+                                              C.c_void_p(totals.ctypes.data), C.byref(st)))
+        return passed[:nf], best[:nf], totals, st.as_dict()
+    return _ScreenFile(filters, arr, str(path).encode(), flags, par, int(batch_bytes))
+
+
+class _ScreenFile(_Owned):
+    """the iterator behind screenFile: one batch per step, tally() for the running summary"""
+
+    _destroy = "btlbf_screen_fastx_close"
+
+    def __init__(self, filters, arr, path, flags, par, batch_bytes):
+        self._L = _lib.load()
+        self._filters = filters  # the handle uses them until close()
+        self.n_filters = len(filters)
+        h = C.c_void_p()
+        check(self._L.btlbf_screen_fastx_open(C.byref(h), arr, self.n_filters, path, flags, C.byref(par), batch_bytes))
+        self._h = h
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if not self._h:
+            raise StopIteration
+        first, n = C.c_uint64(), C.c_uint64()
+        ptrs = [C.c_void_p() for _ in range(3)]
+        check(self._L.btlbf_screen_fastx_next(self._h, C.byref(first), C.byref(n), *[C.byref(p) for p in ptrs]))
+        n = n.value
+        if n == 0:
+            raise StopIteration
+        copy = lambda p, shape: np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), shape=shape).copy()
+        return first.value, copy(ptrs[0], (n, self.n_filters)), copy(ptrs[1], (n,)), copy(ptrs[2], (n,))
+
+    def tally(self):
+        """(passed, best, totals) over the rows delivered so far (btlbf_screen_fastx_tally)"""
+        nf = self.n_filters
+        passed, best, totals = np.zeros(nf, np.uint64), np.zeros(nf, np.uint64), np.zeros(4, np.uint64)
+        check(self._L.btlbf_screen_fastx_tally(self._h, C.c_void_p(passed.ctypes.data), C.c_void_p(best.ctypes.data),
+                                               C.c_void_p(totals.ctypes.data)))
+        return passed, best, totals

@@ -862,6 +862,74 @@ int btlbf_count_windows_seqs(unsigned kmer_size, const char* seq, uint64_t len, 
 int btlbf_count_windows_fastx(const char* path, unsigned kmer_size, uint32_t flags, uint64_t batch_bytes, int device,
                               btlbf_fastx_stats* stats);
 
+/* ---- read screen: every read against several bit filters in one pass ------------------------------------------
+ * What a caller writes around BloomFilter::contains to screen reads against a set of filters (a genome, contaminant
+ * sets): per read and filter, how many of the read's k-mers the filter holds.  One fused kernel hashes every window
+ * once and probes all filters with it (csrc/screen_kernels.hip); more than 8 filters run in groups, hashing once per
+ * group.
+ * screen_seqs : per sequence s of the buffer (layout as btlbf_contains_seqs; NULL: the buffer is one sequence; read_len:
+ *   len / read_len rows) valid[s] = its clean windows and hits[s * n_filters + j] = those of them all of whose bits
+ *   are set in filters[j].  DEFINITION: hits[:, j] and valid equal what btlbf_contains_seqs on filters[j] followed by
+ *   btlbf_count_per_seq returns for the same buffer and layout.  pass_bits (may be NULL): bit j of pass_bits[s] is set
+ *   iff valid[s] > 0 && hits >= p->min_hits && (double)hits >= p->min_fraction * (double)valid (one IEEE double
+ *   multiply, one compare).  The filters are read and never changed; the call always runs the fused direct kernel, never
+ *   the partitioned pipeline, whatever the filters' query mode.
+ *   Refused with BTLBF_EINVAL before any HIP call, outputs untouched: a null argument (pass_bits excepted; seq may be
+ *   null when len == 0); n_filters == 0 or > BTLBF_SCREEN_MAX_FILTERS; a null handle, or the same handle twice; a
+ *   min_fraction outside [0, 1] or NaN; a mem that is neither space; a len that is no multiple of read_len; and then,
+ *   looking at the filters: one that is not BTLBF_BLOOM (counting filters are not screened), or is a shard; filters on
+ *   different devices; filters that differ in kmer_size, in hash_num, or in their spaced seeds (seed strings and h2).
+ *   Every filter's internal lock is held for the whole call, taken in ascending handle address, so that two threads
+ *   screening overlapping sets cannot deadlock.  A pending btlbf_clear is carried out first: a fresh or just-cleared
+ *   filter's column is all zeros.  mem / stream as in btlbf_contains_seqs: BTLBF_HOST stages and returns with the
+ *   results in place; BTLBF_DEVICE runs on the caller's stream and returns with the work queued (the per-window bitmaps
+ *   it reduces live in scratch one of the filters owns, handed from call to call in stream order by an event).  Every
+ *   element of hits, valid and a non-NULL pass_bits is written, and nothing beyond them.
+ * screen_tally : the summary of rows, ADDED to the caller's counts (as btlbf_mibf_classify_tally): passed[j] += rows
+ *   whose bit j is set; best[j] += rows whose passing filter with the most hits is j, ties going to the lowest j;
+ *   totals4 += {rows, rows passing none, rows passing two or more, rows with valid == 0}.  A DEVICE call returns with
+ *   the work queued.
+ * screen_fastx_* : the same over one FASTA / FASTQ file (gzip or not): rows = records, in file order.  Read pairs (two
+ *   files, an interleaved file) are not handled here.
+ *   open : the checks of screen_seqs in the same order -- those that do not look at the filters first, then an unreadable
+ *     path (EIO), then the filters; a device that is not there is BTLBF_EHIP.  The file gets one sequential parser on a thread of its own (the file classifier's
+ *     reader, csrc/fastx_side.hpp) with BTLBF_FASTX_WHOLE always set (flags: BTLBF_FASTX_LINES, BTLBF_FASTX_PAGEABLE), so
+ *     batch_bytes (0 = 64 MiB) must hold the longest record.
+ *   next : one parser batch: bases and offsets go to one of two device slots on a copy stream; on the compute stream
+ *     screen_seqs (BTLBF_DEVICE) under the filters' locks, screen_tally into the handle's running device totals, and the
+ *     copy of the three result arrays into one of two pinned result sets; the call returns with its batch finished, the
+ *     parser thread parses ahead meanwhile.  *first_row is contiguous from 0; *n_rows == 0 at end of input.  The result
+ *     pointers stay valid until the call after the next one.  hits == NULL together with the other two result pointers:
+ *     no per-row copy.  Every row equals screen_seqs over the same reads from memory.  Parser errors come back unchanged
+ *     (BTLBF_EIO for a truncated gzip stream, EINVAL naming the record for one longer than batch_bytes) from the call
+ *     that meets them; rows delivered before stay delivered.  Any error of a batch (the parser's, ENOMEM, a HIP error)
+ *     ends the input: every later call returns it again, so that first_row never skips a batch.
+ *   tally : the running totals so far, in screen_tally's layout.
+ *   screen_fastx : open, next until the end without per-row copies, tally, close.  stats (optional): n_records, n_bases,
+ *     n_batches, n_windows (the sum of valid), seconds_parse, seconds_total; n_hits stays 0. */
+enum { BTLBF_SCREEN_MAX_FILTERS = 16 };
+typedef struct btlbf_screen_params {
+	double min_fraction;
+	uint32_t min_hits;
+	uint32_t reserved;
+} btlbf_screen_params;
+int btlbf_screen_seqs(btlbf_filter* const* filters, unsigned n_filters, const char* seq, uint64_t len,
+                      const btlbf_layout* layout, const btlbf_screen_params* p, uint32_t* hits, uint32_t* valid,
+                      uint32_t* pass_bits, int mem, void* stream);
+int btlbf_screen_tally(const uint32_t* hits, const uint32_t* valid, const uint32_t* pass_bits, uint64_t n_rows,
+                       unsigned n_filters, uint64_t* passed, uint64_t* best, uint64_t* totals4, int mem, int device,
+                       void* stream);
+typedef struct btlbf_screen_file btlbf_screen_file;
+int btlbf_screen_fastx_open(btlbf_screen_file** c, btlbf_filter* const* filters, unsigned n_filters, const char* path,
+                            uint32_t flags, const btlbf_screen_params* p, uint64_t batch_bytes);
+int btlbf_screen_fastx_next(btlbf_screen_file* c, uint64_t* first_row, uint64_t* n_rows, const uint32_t** hits,
+                            const uint32_t** valid, const uint32_t** pass_bits);
+int btlbf_screen_fastx_tally(btlbf_screen_file* c, uint64_t* passed, uint64_t* best, uint64_t* totals4);
+void btlbf_screen_fastx_close(btlbf_screen_file* c);
+int btlbf_screen_fastx(btlbf_filter* const* filters, unsigned n_filters, const char* path, uint32_t flags,
+                       const btlbf_screen_params* p, uint64_t batch_bytes, uint64_t* passed, uint64_t* best,
+                       uint64_t* totals4, btlbf_fastx_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif
