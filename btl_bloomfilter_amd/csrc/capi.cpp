@@ -171,9 +171,10 @@ void fill_hash_params(HashParams& hp, unsigned k, unsigned h)
 	}
 }
 
-// spaced-seed tables on the device; on success the caller owns *d_pos / *d_dc
-int build_spaced(HashParams& hp, const char* const* seeds, unsigned n_seeds, unsigned h2,
-                 uint64_t** d_pos, uint16_t** d_dc)
+// The spaced-seed lists of a configuration, on the host alone: the checks of what the library accepts, the per-seed
+// don't-care lists (dc), the union list (dcu) and the counts in hp that size the kernels' LDS tables.  No device call.
+static int plan_spaced(HashParams& hp, const char* const* seeds, unsigned n_seeds, unsigned h2, std::vector<uint16_t>& dc,
+                       std::vector<uint32_t>& dcu)
 {
 	const unsigned k = hp.k;
 	if (n_seeds == 0 || n_seeds > (unsigned)kMaxSeeds || h2 == 0)
@@ -182,7 +183,6 @@ int build_spaced(HashParams& hp, const char* const* seeds, unsigned n_seeds, uns
 		return fail(BTLBF_EINVAL, "spaced seeds: n_seeds*h2 = %u exceeds %d", n_seeds * h2, kMaxHash);
 	if (k > 1024)
 		return fail(BTLBF_EINVAL, "spaced seeds: k = %u > 1024 unsupported", k);
-	std::vector<uint16_t> dc;
 	for (unsigned j = 0; j < n_seeds; ++j) {
 		if (!seeds[j] || strlen(seeds[j]) != k)
 			return fail(BTLBF_EINVAL, "spaced seed %u must have exactly k = %u characters", j, k);
@@ -193,7 +193,6 @@ int build_spaced(HashParams& hp, const char* const* seeds, unsigned n_seeds, uns
 	}
 	hp.dc_off[n_seeds] = (uint32_t)dc.size();
 	// the union list (internal.hpp HashParams::dcu): distinct offsets with their seed masks, those of every seed first
-	std::vector<uint32_t> dcu;
 	{
 		std::map<unsigned, uint32_t> mask_of;
 		for (unsigned j = 0; j < n_seeds; ++j)
@@ -235,17 +234,40 @@ int build_spaced(HashParams& hp, const char* const* seeds, unsigned n_seeds, uns
 		}
 		hp.n_dcu = (uint32_t)dcu.size();
 	}
-	const size_t dc_bytes = (dc.size() * 2 + 15) / 16 * 16;
+	hp.n_seeds = n_seeds;
+	hp.h2 = h2;
+	hp.h = n_seeds * h2;
+	hp.use_pos_tab = 1; // spaced seeds are masked through the positional table (k <= 1024 checked above)
+	// The positional table and the lists must fit the LDS of the direct kernels next to the tile image (internal.hpp
+	// seq_lds_fits): decided here by arithmetic, so that a configuration is refused when it is set and no launcher ever
+	// asks the runtime for more LDS than a workgroup has.
+	if (!seq_lds_fits(hp))
+		return fail(BTLBF_EINVAL,
+		            "spaced seeds: k = %u with %u seeds (%u don't-care positions in all) needs %u bytes of LDS per workgroup, "
+		            "%u are available",
+		            k, n_seeds, (unsigned)dc.size(), seq_lds_dyn(hp) + kSeqStaticLds, kLdsPerWorkgroup);
+	return BTLBF_OK;
+}
+
+// spaced-seed tables on the device; on success the caller owns *d_pos / *d_dc
+int build_spaced(HashParams& hp, const char* const* seeds, unsigned n_seeds, unsigned h2,
+                 uint64_t** d_pos, uint16_t** d_dc)
+{
+	std::vector<uint16_t> dc;
+	std::vector<uint32_t> dcu;
 	*d_pos = nullptr;
+	{
+		HashParams planned = hp;
+		if (int rc = plan_spaced(planned, seeds, n_seeds, h2, dc, dcu))
+			return rc;
+		hp = planned;
+	}
+	const size_t dc_bytes = (dc.size() * 2 + 15) / 16 * 16;
 	HIP_TRY(hipMalloc((void**)d_dc, dc_bytes + dcu.size() * 4 + 16));
 	if (!dc.empty())
 		HIP_TRY(hipMemcpy(*d_dc, dc.data(), dc.size() * 2, hipMemcpyHostToDevice));
 	if (!dcu.empty())
 		HIP_TRY(hipMemcpy(reinterpret_cast<uint8_t*>(*d_dc) + dc_bytes, dcu.data(), dcu.size() * 4, hipMemcpyHostToDevice));
-	hp.n_seeds = n_seeds;
-	hp.h2 = h2;
-	hp.h = n_seeds * h2;
-	hp.use_pos_tab = 1; // spaced seeds are masked through the positional table (k <= 1024 checked above)
 	hp.dc_idx = *d_dc;
 	hp.dcu = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(*d_dc) + dc_bytes);
 	return BTLBF_OK;
@@ -540,6 +562,24 @@ extern "C" int btlbf_set_query_mode(btlbf_filter* f, int mode)
 	if (is_wide(f) && mode == BTLBF_INSERT_PARTITIONED)
 		return refuse_wide("btlbf_set_query_mode(PARTITIONED)");
 	f->query_mode = mode;
+	return BTLBF_OK;
+}
+
+// planning only (no device needed): would these spaced seeds be accepted, and the LDS they take in the direct kernels
+extern "C" int btlbf_plan_spaced_lds(unsigned kmer_size, const char* const* seeds, unsigned n_seeds, unsigned h2,
+                                     uint32_t* out2)
+{
+	if (!seeds || !out2 || kmer_size == 0 || kmer_size > 32768)
+		return fail(BTLBF_EINVAL, "btlbf_plan_spaced_lds: bad argument");
+	HashParams hp;
+	fill_hash_params(hp, kmer_size, n_seeds * h2);
+	std::vector<uint16_t> dc;
+	std::vector<uint32_t> dcu;
+	out2[0] = 0;
+	out2[1] = kLdsPerWorkgroup;
+	if (int rc = plan_spaced(hp, seeds, n_seeds, h2, dc, dcu))
+		return rc;
+	out2[0] = seq_lds_dyn(hp) + kSeqStaticLds;
 	return BTLBF_OK;
 }
 

@@ -853,6 +853,17 @@ extern "C" int btlbf_plan_read_grid(unsigned kmer_size, unsigned hash_num, unsig
 	return BTLBF_OK;
 }
 
+// planning only (no device needed): does pass A fit the LDS for plain ntHash at this k, and with what front end
+extern "C" int btlbf_plan_pass_a(unsigned kmer_size, unsigned hash_num, unsigned level0_bins, uint32_t* out4)
+{
+	if (!out4 || kmer_size == 0 || hash_num == 0 || level0_bins == 0 || level0_bins > 1024)
+		return fail(BTLBF_EINVAL, "btlbf_plan_pass_a: bad argument");
+	HashParams hp;
+	fill_hash_params(hp, kmer_size, hash_num);
+	part_front_plan(hp, level0_bins, out4);
+	return BTLBF_OK;
+}
+
 extern "C" int btlbf_route_windows(btlbf_filter* f, unsigned n_shards, unsigned* n_windows,
                                    unsigned* shards_per_window)
 {

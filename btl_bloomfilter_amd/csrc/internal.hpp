@@ -98,6 +98,50 @@ struct HashParams {
 };
 static constexpr uint32_t kMaxDcu = 64;
 
+// bytes of dynamic LDS the tile needs (tile bytes + up to 15 bytes of misalignment, rounded to 16)
+__host__ __device__ inline uint32_t seq_tile_cap(uint32_t tile_windows, uint32_t k)
+{
+	return ((tile_windows + k - 1 + 15 + 15) / 16) * 16;
+}
+// bytes of dynamic LDS for the tables that follow the tile: the positional seed table
+// pos_tab[i*8+c] = {srol^(k-1-i)(fwd[c]), srol^i(rev[c])} (when hp.use_pos_tab) and the spaced seeds'
+// don't-care index list
+// (+ one row of zeros behind the k rows: spaced seeds pad their offset list with the "offset" k, whose terms change
+// nothing)
+__host__ __device__ inline uint32_t seq_pos_tab_bytes(const HashParams& hp)
+{
+	return hp.use_pos_tab ? (hp.k + 1) * kNumCodes * 16 : 0;
+}
+__host__ __device__ inline uint32_t seq_dc_list_bytes(const HashParams& hp)
+{
+	return hp.n_seeds ? ((hp.dc_off[hp.n_seeds] * 2 + 15) / 16) * 16 : 0;
+}
+// ... followed by the union list of distinct don't-care offsets (HashParams::dcu), 4 bytes each
+// ... and, where a launcher found room (HashParams::n_pair_rows), the two-base rows of the list's pairs, 256 bytes each
+__host__ __device__ inline uint32_t seq_union_list_bytes(const HashParams& hp)
+{
+	return hp.n_seeds ? ((hp.n_dcu * 4 + 15) / 16) * 16 : 0;
+}
+__host__ __device__ inline uint32_t seq_spaced_bytes(const HashParams& hp)
+{
+	return seq_pos_tab_bytes(hp) + seq_dc_list_bytes(hp) + seq_union_list_bytes(hp) + (hp.n_seeds ? hp.n_pair_rows * 256 : 0);
+}
+
+// The LDS of a workgroup on gfx950, and what the direct sequence kernels take of it (seq_kernels.hip,
+// wide_counter_kernels.hip, mibf_kernels.hip, screen_kernels.hip: 256 threads, tiles of kSeqTileWindows window starts):
+// the tile image and the spaced-seed tables as dynamic LDS, SeqShared and a kernel's own few words as static LDS (1440
+// bytes, 32 more in the miBF kernel; kSeqStaticLds leaves 64 bytes beyond SeqShared for such words, which seq_core.hpp
+// asserts of SeqShared and mibf_kernels.hip of its counters).  Plain ntHash fits
+// at every accepted k (k = 32768: 34848 bytes).  Spaced seeds keep the positional table, (k + 1) * 128 bytes: at
+// k = 1024 the don't-care lists have about 28 KB left, which 16 seeds of low weight exceed.  seq_lds_fits is the
+// one place that decides: build_spaced refuses such seeds with BTLBF_EINVAL and the launchers refuse before they touch a
+// kernel's attributes.
+static constexpr uint32_t kLdsPerWorkgroup = 160 * 1024;
+static constexpr uint32_t kSeqTileWindows = 2048;
+static constexpr uint32_t kSeqStaticLds = 1536;
+inline uint32_t seq_lds_dyn(const HashParams& hp) { return seq_tile_cap(kSeqTileWindows, hp.k) + seq_spaced_bytes(hp); }
+inline bool seq_lds_fits(const HashParams& hp) { return (uint64_t)seq_lds_dyn(hp) + kSeqStaticLds <= kLdsPerWorkgroup; }
+
 // Sequence boundaries inside a buffer (btlbf_layout, device-resident form).
 struct LayoutParams {
 	const uint64_t* starts; // device pointer or nullptr
@@ -246,6 +290,7 @@ static inline uint32_t part_late_cap() { return 32768u; }
 PartTiling part_tiling(const HashParams& hp, uint32_t p0, const LayoutParams& lay, uint64_t len);
 bool part_supported(const HashParams& hp); // can pass A hash this configuration (1..8 hashes; spaced seeds: the union list)
 bool part_hash_fits(const HashParams& hp, uint32_t p0);
+void part_front_plan(const HashParams& hp, uint32_t p0, uint32_t out4[4]); // planning only: btlbf_plan_pass_a
 hipError_t launch_part_hash(const SeqArgs& a, const PartOut& out, uint32_t bin_shift, const PartSide& sd, int query,
                             hipStream_t s);
 // exact != 0: every entry counts (counter increments), so readers honour the exact entry count of a

@@ -480,7 +480,11 @@ hipError_t launch_mibf_seq(MibfOp op, int id_bytes, const MibfArgs& a_in, hipStr
 	uint64_t blocks = n_tiles < max_blocks ? n_tiles : max_blocks;
 	a.tiles_per_block = (n_tiles + blocks - 1) / blocks;
 	blocks = (n_tiles + a.tiles_per_block - 1) / a.tiles_per_block;
-	const size_t dyn = seq_tile_cap(kMTile, a.hp.k) + seq_spaced_bytes(a.hp);
+	static_assert(kMTile == (int)kSeqTileWindows, "seq_lds_dyn counts this kernel's tile");
+	static_assert(sizeof(SeqShared) + 4 * sizeof(unsigned long long) <= kSeqStaticLds, "kSeqStaticLds covers SeqShared and wg_cnt");
+	if (!seq_lds_fits(a.hp)) // (build_spaced refuses such seeds with a message; nothing is launched or configured here)
+		return hipErrorInvalidValue;
+	const size_t dyn = seq_lds_dyn(a.hp);
 	const int hs = a.hp.n_seeds ? (int)a.hp.h : 0;
 	auto go = [&](auto kernel) -> hipError_t {
 		if (dyn > 48 * 1024) {

@@ -522,6 +522,29 @@ bool part_hash_fits(const HashParams& hp, uint32_t p0)
 	return part_front(hp, p0, fr);
 }
 
+// ragged layout, plain tiles: words of the overlapped schedule's start bitmap behind the tile image (one bit per staged
+// byte), or 0 where the LDS has no room for it without giving up the positional table
+static uint32_t part_start_bitmap_words(const HashParams& hp, uint32_t p0)
+{
+	PartFront plain, fr;
+	const uint32_t words = ((uint32_t)kPartTile + hp.k + 2 + 31) / 32, cap = seq_tile_cap(kPartTile, hp.k);
+	const uint32_t sb_bytes = (words * 4 + 15) / 16 * 16;
+	if (part_front(hp, p0, plain) && part_front(hp, p0, fr, cap + sb_bytes) && fr.use_pos_tab == plain.use_pos_tab)
+		return sb_bytes / 4;
+	return 0;
+}
+
+// planning only: { pass A fits, its dynamic LDS with a plain tile, positional table used, start bitmap words (ragged) }
+void part_front_plan(const HashParams& hp, uint32_t p0, uint32_t out4[4])
+{
+	PartFront fr;
+	const bool fits = part_front(hp, p0, fr);
+	out4[0] = fits;
+	out4[1] = fits ? fr.dyn : 0;
+	out4[2] = fits ? fr.use_pos_tab : 0;
+	out4[3] = fits ? part_start_bitmap_words(hp, p0) : 0;
+}
+
 // The read grid for (hash configuration, level-0 bins, layout), if it pays: uniform reads, the tile image fits
 // the LDS next to the rings, and the lanes it keeps busy beat plain tiles by 5 %.
 bool part_read_grid(const HashParams& hp, uint32_t p0, const LayoutParams& lay, PartGrid* g)
@@ -611,14 +634,7 @@ hipError_t launch_part_hash(const SeqArgs& a_in, const PartOut& out, uint32_t bi
 		return hipErrorInvalidValue;
 	// ragged layout: room for the start bitmap of the overlapped schedule behind the tile image, if the LDS has it
 	// without giving up the positional table (part_hash_inst.hip; the plain kernels leave it unused)
-	a.sb_words = 0;
-	if (a.layout.starts && !grid) {
-		PartFront plain;
-		const uint32_t words = ((uint32_t)kPartTile + a.hp.k + 2 + 31) / 32, cap = seq_tile_cap(kPartTile, a.hp.k);
-		const uint32_t sb_bytes = (words * 4 + 15) / 16 * 16;
-		if (part_front(a.hp, out.P, plain) && part_front(a.hp, out.P, fr, cap + sb_bytes) && fr.use_pos_tab == plain.use_pos_tab)
-			a.sb_words = sb_bytes / 4;
-	}
+	a.sb_words = a.layout.starts && !grid ? part_start_bitmap_words(a.hp, out.P) : 0;
 	const uint32_t tile_lds = grid ? g.cap : a.sb_words ? seq_tile_cap(kPartTile, a.hp.k) + a.sb_words * 4 : 0;
 	a.hp.n_pair_rows = 0; // (everything above was planned without them)
 	if (!part_front(a.hp, out.P, fr, tile_lds))

@@ -241,7 +241,10 @@ hipError_t launch_screen(const ScreenArgs& a_in, hipStream_t s)
 	uint64_t blocks = a.n_tiles < max_blocks ? a.n_tiles : max_blocks;
 	a.tiles_per_block = (a.n_tiles + blocks - 1) / blocks;
 	blocks = (a.n_tiles + a.tiles_per_block - 1) / a.tiles_per_block;
-	const size_t dyn = seq_tile_cap(kScreenTile, a.hp.k) + seq_spaced_bytes(a.hp);
+	static_assert(kScreenTile == (int)kSeqTileWindows, "seq_lds_dyn counts this kernel's tile");
+	if (!seq_lds_fits(a.hp)) // (build_spaced refuses such seeds with a message; nothing is launched or configured here)
+		return hipErrorInvalidValue;
+	const size_t dyn = seq_lds_dyn(a.hp);
 	const dim3 grid((unsigned)blocks);
 	switch (a.nf) {
 	case 1: return screen_launch_nf<1>(a, s, grid, dyn);

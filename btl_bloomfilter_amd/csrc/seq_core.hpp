@@ -56,34 +56,9 @@ __device__ __forceinline__ uint8_t base_entry(uint32_t c)
 	}
 }
 
-// bytes of dynamic LDS the tile needs (tile bytes + up to 15 bytes of misalignment, rounded to 16)
-__host__ __device__ inline uint32_t seq_tile_cap(uint32_t tile_windows, uint32_t k)
-{
-	return ((tile_windows + k - 1 + 15 + 15) / 16) * 16;
-}
-// bytes of dynamic LDS for the tables that follow the tile: the positional seed table
-// pos_tab[i*8+c] = {srol^(k-1-i)(fwd[c]), srol^i(rev[c])} (when hp.use_pos_tab) and the spaced seeds'
-// don't-care index list
-// (+ one row of zeros behind the k rows: spaced seeds pad their offset list with the "offset" k, whose terms change
-// nothing)
-__host__ __device__ inline uint32_t seq_pos_tab_bytes(const HashParams& hp)
-{
-	return hp.use_pos_tab ? (hp.k + 1) * kNumCodes * 16 : 0;
-}
-__host__ __device__ inline uint32_t seq_dc_list_bytes(const HashParams& hp)
-{
-	return hp.n_seeds ? ((hp.dc_off[hp.n_seeds] * 2 + 15) / 16) * 16 : 0;
-}
-// ... followed by the union list of distinct don't-care offsets (HashParams::dcu), 4 bytes each
-// ... and, where a launcher found room (HashParams::n_pair_rows), the two-base rows of the list's pairs, 256 bytes each
-__host__ __device__ inline uint32_t seq_union_list_bytes(const HashParams& hp)
-{
-	return hp.n_seeds ? ((hp.n_dcu * 4 + 15) / 16) * 16 : 0;
-}
-__host__ __device__ inline uint32_t seq_spaced_bytes(const HashParams& hp)
-{
-	return seq_pos_tab_bytes(hp) + seq_dc_list_bytes(hp) + seq_union_list_bytes(hp) + (hp.n_seeds ? hp.n_pair_rows * 256 : 0);
-}
+// (the dynamic LDS of the tile image and of the tables behind it -- seq_tile_cap, seq_pos_tab_bytes, seq_dc_list_bytes,
+// seq_union_list_bytes, seq_spaced_bytes -- is counted in internal.hpp, where the host side can see it too)
+static_assert(sizeof(SeqShared) + 64 <= kSeqStaticLds, "kSeqStaticLds covers SeqShared and a kernel's own few words");
 
 // one-time table setup; callers __syncthreads() before first use (seq_stage_tile does)
 template <int NT, bool SPACED>

@@ -417,7 +417,10 @@ hipError_t launch_seq_op(int op, const SeqArgs& a_in, hipStream_t s)
 	uint64_t blocks = a.n_tiles < max_blocks ? a.n_tiles : max_blocks;
 	a.tiles_per_block = (a.n_tiles + blocks - 1) / blocks;
 	blocks = (a.n_tiles + a.tiles_per_block - 1) / a.tiles_per_block;
-	size_t dyn = seq_tile_cap(kTile, a.hp.k) + seq_spaced_bytes(a.hp);
+	static_assert(kTile == (int)kSeqTileWindows, "seq_lds_dyn counts this kernel's tile");
+	if (!seq_lds_fits(a.hp)) // (build_spaced refuses such seeds with a message; nothing is launched or configured here)
+		return hipErrorInvalidValue;
+	size_t dyn = seq_lds_dyn(a.hp);
 	dim3 grid((unsigned)blocks);
 	switch (op) {
 	case OP_BF_INSERT: return launch_one<OP_BF_INSERT>(a, s, grid, dyn);

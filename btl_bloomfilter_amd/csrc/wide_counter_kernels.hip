@@ -225,7 +225,10 @@ hipError_t launch_wide_seq_op(int op, int bytes, const SeqArgs& a_in, hipStream_
 	uint64_t blocks = a.n_tiles < max_blocks ? a.n_tiles : max_blocks;
 	a.tiles_per_block = (a.n_tiles + blocks - 1) / blocks;
 	blocks = (a.n_tiles + a.tiles_per_block - 1) / a.tiles_per_block;
-	const size_t dyn = seq_tile_cap(kWideTile, a.hp.k) + seq_spaced_bytes(a.hp);
+	static_assert(kWideTile == (int)kSeqTileWindows, "seq_lds_dyn counts this kernel's tile");
+	if (!seq_lds_fits(a.hp)) // (build_spaced refuses such seeds with a message; nothing is launched or configured here)
+		return hipErrorInvalidValue;
+	const size_t dyn = seq_lds_dyn(a.hp);
 	const dim3 grid((unsigned)blocks);
 	switch (bytes) {
 	case 2: return wide_launch_op<2>(op, a, s, grid, dyn);

@@ -50,6 +50,26 @@
  *    reference accepts (seedTab != 0, vendor/nthash.hpp:195-228: A C G T U, either case, and
  *    the raw bytes 1 3 4 5 7) and it does not cross a sequence boundary.  Exactly the clean
  *    windows are the k-mers ntHashIterator emits (vendor/ntHashIterator.hpp:59-86).
+ *  - k-mer sizes: btlbf_create, btlbf_create_shard, btlbf_load, btlbf_hash_seqs and btlbf_hash_kmers take
+ *    kmer_size 1 .. 32768 and return BTLBF_EINVAL outside; every sequence and raw-k-mer call of a filter works over
+ *    that whole range (plain ntHash above k = 128 starts each lane's first window by Horner's rule instead of from
+ *    a positional table).  The miBF calls take the k of their stage-1 filter; the btlbf_count_windows_* calls,
+ *    which do not hash, take any k from 1 to 2^31 - 1.
+ *    Spaced seeds (btlbf_set_spaced_seeds, btlbf_hash_seqs with seeds, btlbf_mibf_create over such a filter) take
+ *    k <= 1024, and their tables must fit the 160 KB of LDS of a workgroup next to the tile image:
+ *      floor16(2048 + k + 29) + (k + 1) * 128 + ceil16(2 * D) + ceil16(4 * U) + 1536 <= 163840
+ *    with D = don't-care positions summed over the seeds and U = entries of the list of distinct don't-care
+ *    offsets (kept only when it has at most 64 entries, fillers included; else 0).  Up to k = 900 every seed set
+ *    fits; at k = 1024, D <= 14008 (16 seeds of weight 2 have 16352).  A seed set beyond that is refused with
+ *    BTLBF_EINVAL by the call that sets it -- the message names k, the seed count and the bytes asked for and
+ *    available -- before anything is allocated or launched; btlbf_plan_spaced_lds gives the same answer without a
+ *    device.
+ *    The partitioned pipeline (btlbf_set_insert_mode / btlbf_set_query_mode, PARTITIONED or AUTO) hashes in its
+ *    pass A, whose tile image shares the LDS with the partitioning rings: plain ntHash fits up to k = 16098 with
+ *    32 level-0 bins, 13410 with 256, 10338 with 512 and 4194 with 1024 bins (btlbf_plan_pass_a tells for a given
+ *    k and bin count).  Above that a call in either mode is carried out by the direct kernels, with the
+ *    same result; the profile (btlbf_get_profile) shows insert_direct / query_direct instead of insert_hash /
+ *    query_hash.  tests/test_gpu_large_k.py holds the calls to all of this on either side of each size.
  *  - sequence boundaries inside a buffer are described by a btlbf_layout:
  *      starts != NULL : n_seqs+1 ascending byte offsets (starts[0]=0 .. starts[n_seqs]=len)
  *      else read_len>0: back-to-back reads of exactly read_len bytes (len % read_len == 0)
@@ -655,6 +675,17 @@ int btlbf_resolve_seqs(btlbf_filter* f, const char* seq, uint64_t len, const btl
    when plain tiles are used instead (ragged input, reads too short / too long, no gain). */
 int btlbf_plan_read_grid(unsigned kmer_size, unsigned hash_num, unsigned read_len, unsigned level0_bins,
                          uint32_t* out4);
+
+/* Planning only, no device needed: pass A's front end for plain ntHash at kmer_size with `level0_bins` level-0 bins:
+   out4 = { 1 if pass A fits the LDS (0: the partitioned modes hand the call to the direct kernels), bytes of dynamic
+   LDS it asks for with a plain tile, 1 if the positional seed table is used, words of the ragged layout's start
+   bitmap (0: no room, the plain schedule runs) }.  See "k-mer sizes" above. */
+int btlbf_plan_pass_a(unsigned kmer_size, unsigned hash_num, unsigned level0_bins, uint32_t* out4);
+
+/* Planning only, no device needed: what btlbf_set_spaced_seeds, btlbf_hash_seqs and btlbf_mibf_create would make of
+   these spaced seeds.  out2 = { bytes of LDS per workgroup the direct kernels need with them (0 when refused for
+   another reason), bytes available }.  Returns BTLBF_EINVAL, with the same message, exactly when those calls do. */
+int btlbf_plan_spaced_lds(unsigned kmer_size, const char* const* seeds, unsigned n_seeds, unsigned h2, uint32_t* out2);
 
 /* number of set bits in a device buffer of nbytes (multiple of 8, e.g. a hit bitmap); synchronises the stream */
 int btlbf_popcount_bits(const void* dev_buf, uint64_t nbytes, uint64_t* out, int device, void* stream);

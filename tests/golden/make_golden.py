@@ -318,9 +318,40 @@ def kmer_path():
           out["swig_test_pl"]["pop"], "same as iterator path:", out["swig_test_pl"]["same_as_iterator_path"])
 
 
+def large_k():
+    """large_k.json: ntHashIterator, stHashIterator and the raw-k-mer path at the k-mer sizes where the GPU kernels
+    change their code path (tests/large_k_cases.py golden_cases: k up to 32768).  Per case the recipe of the input (seed,
+    length, alphabet, lowercase run, the bytes put in afterwards), the parameters, the number of emitted positions and
+    the SHA-256 of the positions, hash values and strands the reference returns (little-endian uint64) -- digests only."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import large_k_cases as lk
+    from oracle.pyoracle import Oracle
+
+    ref, oracle = Ref(), Oracle()
+    out = {}
+    for case in lk.golden_cases():
+        if case["kind"] == "kmer":
+            # the reference's 2-/3-base tail tables are indexed out of range by some bytes; which k-mers have a value at
+            # all is the oracle's `defined` (as in kmer_path.json), the values are the reference's
+            got, _, ok = lk.kmer_case_outputs(oracle, case, ref)
+            extra = dict(defined=[int(x) for x in ok])
+        else:
+            got, extra = lk.run_case(ref, case), {}
+        rec = {key: case[key] for key in case if key != "name"}
+        rec.update(extra)
+        rec["expected"] = lk.digest_case(got)
+        out[case["name"]] = rec
+        print(case["name"], rec["expected"]["n"], flush=True)
+    with open(os.path.join(HERE, "large_k.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "kmer":
         kmer_path()  # only kmer_path.json (added in round 3; the other fixtures are left as they are)
+    elif len(sys.argv) > 1 and sys.argv[1] == "large_k":
+        large_k()  # only large_k.json
     else:
         main()
         kmer_path()

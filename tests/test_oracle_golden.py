@@ -102,6 +102,26 @@ def test_kmer_path_swig_test_pl_replay(oracle):
     assert oracle.bf_contains(filt, s["bits"], s["h"], qh).tolist() == s["contains"]
 
 
+def test_large_k_digests(oracle):
+    """tests/golden/large_k.json: the reference's hash streams at k = 129 .. 32768 (plain ntHash, spaced seeds up to
+    k = 1024, raw k-mers), pinned by SHA-256 over inputs rebuilt from their recipes.  This is what lets the GPU tests at
+    these sizes (tests/test_gpu_large_k.py) trust the oracle on a machine without the reference."""
+    import large_k_cases as lk
+
+    g = load_golden(lk.GOLDEN_FILE)
+    cases = lk.golden_cases()
+    assert sorted(g) == sorted(c["name"] for c in cases) and len(cases) == 21
+    for case in cases:
+        rec = g[case["name"]]
+        assert {key: rec[key] for key in case if key != "name"} == {key: case[key] for key in case if key != "name"}, case["name"]
+        if case["kind"] == "kmer":
+            got, _, ok = lk.kmer_case_outputs(oracle, case)
+            assert ok.tolist() == rec["defined"]
+        else:
+            got = lk.run_case(oracle, case)
+        assert got["pos"].size > 0 and lk.digest_case(got) == rec["expected"], case["name"]
+
+
 def _body(path):
     raw = open(path, "rb").read()
     i = raw.index(b"[HeaderEnd]\n") + len(b"[HeaderEnd]\n")

@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 from conftest import GOLDEN, load_golden
 
+import large_k_cases as lk
+
 GOLDEN_FILE = "oracle_vs_ref.json"
 RECORD = bool(os.environ.get("BTLBF_RECORD_REF_GOLDEN"))
 
@@ -121,6 +123,34 @@ def test_sthash_random(oracle, ref_or_none, pinned, k, h2):
             assert all((x == y).all() for x, y in zip(a, b))
             exp += list(b)
     pinned("sthash_k%d_h2%d" % (k, h2), got, exp if ref else None)
+
+
+# ---- large k: the sizes at which the GPU kernels change their code path (tests/test_gpu_large_k.py) ----------------
+# Live against the genuine reference only (the `ref` fixture skips without oracle/_ref); tests/golden/large_k.json and
+# test_oracle_golden.py carry the same pin to machines without it.  Every input holds an N, a lowercase run and one of
+# the raw bytes 1 3 4 5 7 (large_k_cases.seq_recipe).
+@pytest.mark.parametrize("case", [c for c in lk.golden_cases() if c["kind"] != "kmer"], ids=lambda c: c["name"])
+def test_large_k_hash_streams(oracle, ref, case):
+    a, b = lk.run_case(oracle, case), lk.run_case(ref, case)
+    s = lk.build_input(case["input"])
+    assert lk.N in s and any(x in s for x in lk.RAW_BYTES) and s != s.upper()
+    # windows on either side of the N, none across it
+    p = [q for q, byte in case["input"]["bytes"] if byte == lk.N][0]
+    pos = a["pos"].astype(np.int64)
+    assert (pos < p - case["k"] + 1).any() and (pos > p).any() and not ((pos > p - case["k"]) & (pos <= p)).any()
+    for key in b:
+        assert a[key].shape == b[key].shape and (a[key] == b[key]).all(), (case["name"], key)
+    assert lk.digest_case(a) == load_golden(lk.GOLDEN_FILE)[case["name"]]["expected"]
+
+
+@pytest.mark.parametrize("case", [c for c in lk.golden_cases() if c["kind"] == "kmer"], ids=lambda c: c["name"])
+def test_large_k_kmer_path(oracle, ref, case):
+    """raw k-mers at k = 1023 (k % 4 == 3), 1024 and 32768 (0), 4097 (1): lowercase, U, an N, a raw byte"""
+    a, hv, ok = lk.kmer_case_outputs(oracle, case)
+    b, _, _ = lk.kmer_case_outputs(oracle, case, ref)
+    assert ok.sum() >= 6, ok
+    assert (a["hashes"] == b["hashes"]).all(), case["name"]
+    assert lk.digest_case(a) == load_golden(lk.GOLDEN_FILE)[case["name"]]["expected"]
 
 
 @pytest.mark.parametrize("bits", [64, 1000, 1 << 16, 999992])

@@ -23,7 +23,7 @@ def rand_reads(rng, n_reads, L, p_bad):
 def one_case(rng, it):
     lg = int(rng.integers(10, 34))
     bits = (1 << lg) if rng.random() < 0.6 else int(rng.integers(1 << (lg - 1), 1 << lg)) // 64 * 64 + 64
-    k = int(rng.choice([1, 4, 5, 11, 21, 25, 31, 32, 33, 47, 64, 96, 150]))
+    k = int(rng.choice([1, 4, 5, 11, 21, 25, 31, 32, 33, 47, 64, 96, 150, 257, 1011, 2049]))
     h = int(rng.integers(1, 9))
     L = int(rng.choice([k, k + 1, 50, 100, 150, 151, 250, 1000]))
     L = max(L, k)
@@ -33,7 +33,7 @@ def one_case(rng, it):
         reads[rng.integers(0, n_reads, n_reads // 2)] = reads[0]
     counting = rng.random() < 0.25
     seeds, h2 = None, 1
-    if not counting and k >= 4 and rng.random() < 0.2:  # spaced seeds (stHashIterator): h = n_seeds * h2
+    if not counting and 4 <= k <= 1024 and rng.random() < 0.2:  # spaced seeds (stHashIterator, k <= 1024): h = n_seeds * h2
         n_seeds, h2 = int(rng.integers(1, 4)), int(rng.integers(1, 3))
         h = n_seeds * h2
         seeds = []
