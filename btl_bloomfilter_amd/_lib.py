@@ -21,6 +21,8 @@ FASTX_LINES, FASTX_PAGEABLE, FASTX_WHOLE, CLASSIFY_INTERLEAVED = 1, 2, 4, 1 << 8
 MIBF_ID_PER_FILE, MIBF_ID_PER_RECORD = 0, 1
 MIBF_SAT_NONE, MIBF_SAT_SERIAL, MIBF_SAT_PARALLEL = 0, 1, 2
 SCREEN_MAX_FILTERS = 16
+COMBINE_OR, COMBINE_AND, COMBINE_ANDNOT, COMBINE_ADD, COMBINE_MAX, COMBINE_MIN = range(6)
+COMBINE_MAX_SRCS = 16
 PROF_SLOTS = 10
 PROF_NAMES = ["insert_direct", "query_direct", "insert_hash", "insert_split", "insert_apply", "query_hash",
               "query_split", "query_test", "query_resolve", "other"]
@@ -115,6 +117,10 @@ _PROTOS = {
     "btlbf_set_spaced_seeds": (C.c_int, [_P, C.POINTER(C.c_char_p), C.c_uint, C.c_uint]),
     "btlbf_digest": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "btlbf_compare": (C.c_int, [_P, _P, C.POINTER(C.c_uint64)]),
+    "btlbf_clone": (C.c_int, [C.POINTER(_P), _P]),
+    "btlbf_combine": (C.c_int, [_P, C.POINTER(_P), C.c_uint, C.c_int, C.POINTER(C.c_uint64)]),
+    "btlbf_fold": (C.c_int, [C.POINTER(_P), _P, C.c_uint64]),
+    "btlbf_threshold_bits": (C.c_int, [C.POINTER(_P), _P, C.c_uint]),
     "btlbf_rank_create": (C.c_int, [C.POINTER(_P), _P]),
     "btlbf_rank_destroy": (None, [_P]),
     "btlbf_rank_ones": (C.c_uint64, [_P]),

@@ -14,13 +14,13 @@ CSRC = os.path.join(HERE, "csrc")
 TAG = os.environ.get("BTLBF_BUILD_TAG", "")
 OBJ = os.path.join(HERE, "_build" + ("_" + TAG if TAG else ""))
 LIB = os.path.join(HERE, "libbtlbf%s.so" % ("_" + TAG if TAG else ""))
-HEADERS = ["internal.hpp", "mibf_plan.hpp", "fastx_side.hpp", "part_plan.hpp", "mibf_zip.hpp", "mibf_classify_core.hpp", "host_internal.hpp", "host_partition.hpp", "device_utils.hpp", "seq_core.hpp", "partition_core.hpp", "wide_counter.hpp", "screen_plan.hpp",
+HEADERS = ["internal.hpp", "mibf_plan.hpp", "fastx_side.hpp", "part_plan.hpp", "mibf_zip.hpp", "mibf_classify_core.hpp", "host_internal.hpp", "host_partition.hpp", "device_utils.hpp", "seq_core.hpp", "partition_core.hpp", "wide_counter.hpp", "screen_plan.hpp", "fold_plan.hpp", "algebra_swar.hpp",
            os.path.join("..", "..", "include", "btlbf.h")]
 # host units (the C ABI over host_internal.hpp) and kernel units; tools/sanitize_host.sh reads both lists
 HOST_UNITS = ["capi", "host_io", "host_seq", "host_query", "host_partition", "host_aux", "host_mibf", "host_mibf_probs",
-              "host_mibf_fastx", "host_mibf_build", "host_screen", "fastx"]
+              "host_mibf_fastx", "host_mibf_build", "host_screen", "host_algebra", "fastx"]
 KERNEL_UNITS = ["seq_kernels", "aux_kernels", "split_query_kernels", "partition_kernels", "mibf_kernels", "mibf_classify_kernels",
-                "mibf_classify_pair_kernels", "mibf_stream_kernels", "mibf_build_kernels", "wide_counter_kernels", "screen_kernels"]
+                "mibf_classify_pair_kernels", "mibf_stream_kernels", "mibf_build_kernels", "wide_counter_kernels", "screen_kernels", "algebra_kernels"]
 # (object name, source, extra flags): pass A of the partitioned pipeline is one unit per hash count
 UNITS = [(u, u + ".cpp", []) for u in HOST_UNITS] + [(u, u + ".hip", []) for u in KERNEL_UNITS]
 UNITS += [("part_hash_h%d" % h, "part_hash_inst.hip", ["-DBTLBF_PART_H=%d" % h]) for h in range(1, 9)]

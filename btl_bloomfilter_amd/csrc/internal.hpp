@@ -508,4 +508,25 @@ hipError_t launch_screen_tally(const uint32_t* hits, const uint32_t* valid, cons
                                uint32_t n_filters, unsigned long long* passed, unsigned long long* best,
                                unsigned long long* totals4, unsigned long long* windows, hipStream_t s);
 
+// the filter algebra (algebra_kernels.hip): streaming kernels that WRITE a filter.  `counter_bytes` is 0 for a bit filter,
+// else the counter's width; every array is 16-byte aligned and a multiple of 16 bytes long, its padding zero.
+static constexpr unsigned kCombineMaxSrcs = 16; // BTLBF_COMBINE_MAX_SRCS
+struct CombineSrcs {
+	const void* p[kCombineMaxSrcs];
+};
+// dst = dst OP srcs.p[0] OP ... OP srcs.p[n - 1] over nbytes, in one pass; *pop += set bits / non-zero counters of the
+// result.  op is a BTLBF_COMBINE_* that belongs to the kind (the caller has checked)
+hipError_t launch_combine(int counter_bytes, int op, void* dst, const CombineSrcs& srcs, unsigned n, uint64_t nbytes,
+                          unsigned long long* pop, hipStream_t s);
+// Row g of dst (rows are row_bytes / 16 vectors of 16 bytes, row_bytes apart) = the combination (OR / saturating add) of
+// slices [g * per_group, min((g + 1) * per_group, n_slices)) of src, where slice j is the `valid` bytes from byte
+// j * stride on -- at any alignment; what lies behind them in a slice's last vector is masked off.  src must hold
+// (n_slices - 1) * stride + valid bytes.  Every byte of every row is written.
+hipError_t launch_fold(int counter_bytes, const void* src, uint64_t stride, uint64_t valid, uint64_t n_slices,
+                       uint64_t per_group, uint64_t groups, void* dst, uint64_t row_bytes, hipStream_t s);
+// bit p of out = counter p of src >= threshold (threshold >= 1), for all out_words 64-bit words of out: counters from
+// src_bytes on count as zero
+hipError_t launch_threshold_bits(int counter_bytes, const void* src, uint64_t src_bytes, uint64_t threshold, void* out,
+                                 uint64_t out_words, hipStream_t s);
+
 } // namespace btlbf

@@ -103,6 +103,8 @@ def _out(b, shape, dtype):
 
 
 _MODES = {"auto": 0, "direct": 1, "partitioned": 2}
+_COMBINE = {"or": _lib.COMBINE_OR, "and": _lib.COMBINE_AND, "andnot": _lib.COMBINE_ANDNOT, "add": _lib.COMBINE_ADD,
+            "max": _lib.COMBINE_MAX, "min": _lib.COMBINE_MIN}
 
 
 def _mode(mode):
@@ -202,6 +204,37 @@ class _Filter(_Owned):
         out = (C.c_uint64 * 2)()
         check(self._L.btlbf_digest(self._h, out))
         return int(out[0]), int(out[1])
+
+    # -- filter algebra (btlbf_clone / btlbf_combine / btlbf_fold / btlbf_threshold_bits) ----------------
+    def _derived(self, handle):
+        """a filter of this one's class around a handle the library made from it"""
+        f = object.__new__(type(self))
+        f.__dict__.update({k: v for k, v in self.__dict__.items() if k != "_h"})
+        _Filter.__init__(f, handle)
+        return f
+
+    def copy(self):
+        """a second filter with the same geometry, settings and body, copied in HBM (btlbf_clone)"""
+        h = C.c_void_p()
+        check(self._L.btlbf_clone(C.byref(h), self._h))
+        return self._derived(h)
+
+    def combine(self, others, op):
+        """self = self OP others[0] OP ... in one pass over HBM (btlbf_combine; op: a _lib.COMBINE_* or its name);
+        returns the popcount of the result (set bits / non-zero counters)"""
+        others = list(others)
+        arr = (C.c_void_p * max(len(others), 1))(*[o._h for o in others])
+        pop = C.c_uint64()
+        check(self._L.btlbf_combine(self._h, arr, len(others), _COMBINE[op] if isinstance(op, str) else int(op),
+                                    C.byref(pop)))
+        return pop.value
+
+    def fold(self, factor):
+        """the filter of size / factor positions that the same data would have built (btlbf_fold): bit filters
+        exactly; counting filters exactly for incrementAll, as an upper bound for incrementMin"""
+        h = C.c_void_p()
+        check(self._L.btlbf_fold(C.byref(h), self._h, int(factor)))
+        return self._derived(h)
 
     def setInsertMode(self, mode, scratch_bytes=0):
         """'auto' | 'direct' | 'partitioned' (see btlbf_set_insert_mode)"""
@@ -346,6 +379,32 @@ class BloomFilter(_Filter):
     def insertAndCheckSeqs(self, seq, starts=None, read_len=0, want_valid=True, want_counts=False, stream=None):
         return self._query(self._L.btlbf_insert_and_check_seqs, seq, starts, read_len, want_valid, want_counts,
                            stream)
+
+    # set operations with filters of the same geometry, in place (each is one pass whatever the number of operands)
+    def union(self, *others):
+        self.combine(others, _lib.COMBINE_OR)
+        return self
+
+    def intersect(self, *others):
+        self.combine(others, _lib.COMBINE_AND)
+        return self
+
+    def subtract(self, *others):
+        self.combine(others, _lib.COMBINE_ANDNOT)
+        return self
+
+    __ior__ = union
+    __iand__ = intersect
+    __isub__ = subtract
+
+    def __or__(self, other):
+        return self.copy().union(other)
+
+    def __and__(self, other):
+        return self.copy().intersect(other)
+
+    def __sub__(self, other):
+        return self.copy().subtract(other)
 
     def microbench(self, kind, n_access):
         done = C.c_uint64()
@@ -501,6 +560,21 @@ class CountingBloomFilter(_Filter):
 
     def filtered_FPR(self):
         return (self.filtered_popcount() / self.size()) ** self.getHashNum()
+
+    def merge(self, *others, op="add"):
+        """self = self OP others, counter by counter, in place: "add" saturates at the counter's maximum (what
+        incrementAll of all the inputs into one filter leaves), "max", "min".  Returns self."""
+        if op not in ("add", "max", "min"):
+            raise ValueError("merge: op must be 'add', 'max' or 'min'")
+        self.combine(others, op)
+        return self
+
+    def toBloomFilter(self, threshold=None):
+        """the BloomFilter of size() bits with bit p = (counter p >= threshold) (default: the filter's own threshold): its
+        contains() is this filter's at that threshold, in 1/8 to 1/64 of the memory (btlbf_threshold_bits)"""
+        h = C.c_void_p()
+        check(self._L.btlbf_threshold_bits(C.byref(h), self._h, 0 if threshold is None else int(threshold)))
+        return BloomFilter(_handle=h)
 
     def insert(self, hashes, serial=False, stream=None):  # = incrementMin (CountingBloomFilter.hpp:198-204)
         self.incrementMin(hashes, serial, stream)

@@ -30,7 +30,8 @@
  *    from two streams without an event between them is the caller's race.  The calls whose results are
  *    host-visible and that take no stream wait for ALL streams of the device before they look at the array:
  *    btlbf_download, btlbf_upload, btlbf_store / btlbf_store_shard, the judges (btlbf_popcount,
- *    btlbf_filtered_popcount, btlbf_digest, btlbf_compare), btlbf_rank_create, btlbf_mibf_create and
+ *    btlbf_filtered_popcount, btlbf_digest, btlbf_compare), the filter algebra (btlbf_clone, btlbf_combine,
+ *    btlbf_fold, btlbf_threshold_bits), btlbf_rank_create, btlbf_mibf_create and
  *    btlbf_mibf_load; asynchronous DEVICE calls on any stream may precede them without a synchronisation by the
  *    caller.  tests/test_gpu_stream_order.py holds the calls to this with inputs that are still in flight on a
  *    non-blocking stream when the call is issued.
@@ -385,6 +386,57 @@ int btlbf_digest(btlbf_filter* f, uint64_t* out2);
  * out3 = {bits that differ, bits set only in a, bits set only in b}; counting filters: {counters that
  * differ, counters with a > b, counters with a < b}, per counter of the filter's width.  Synchronises the device. */
 int btlbf_compare(btlbf_filter* a, btlbf_filter* b, uint64_t* out3);
+
+/* ---- filter algebra: combining filters that exist ---------------------------------------------------------
+ * The reference has no such operations: its users loop over getFilter() on the host (BloomFilter.hpp:373).  Here the
+ * arrays stay in HBM.  The contract is exact arithmetic on positions (bits, or counters of the filter's width); since
+ * positions are hash % m_size (BloomFilter.hpp:190, CountingBloomFilter.hpp:52-58) it implies three identities against
+ * filters BUILT by the calls above: the union of two bit filters is the filter built from both inputs; a filter of m
+ * positions folds into the filter built at m / factor; the thresholded counting filter answers contains() as the
+ * counting filter does at that threshold (CountingBloomFilter.hpp:190-196).
+ * All four calls are synchronous like btlbf_compare: they synchronise the device, run on the null stream and return when
+ * done.  A pending btlbf_clear of an operand takes effect first.  Every refusal below is BTLBF_EINVAL before any HIP
+ * call, with no filter touched, *out set to NULL (where there is one) and the reason in btlbf_last_error(). */
+enum { BTLBF_COMBINE_OR = 0, BTLBF_COMBINE_AND = 1, BTLBF_COMBINE_ANDNOT = 2,   /* bit filters */
+       BTLBF_COMBINE_ADD = 3, BTLBF_COMBINE_MAX = 4, BTLBF_COMBINE_MIN = 5 };   /* counting filters, every width */
+#define BTLBF_COMBINE_MAX_SRCS 16
+
+/* A second filter of the same kind, geometry, shard range, device, threshold, spaced seeds, nEntry / tEntry / dFPR and
+ * BitsPerCounter echo, its body copied device to device (a cleared source gives a cleared clone, without a copy).  Insert
+ * and query modes are the defaults of a new filter; scratch and profile are not copied.  Refused: a null argument. */
+int btlbf_clone(btlbf_filter** out, btlbf_filter* f);
+
+/* dst = dst OP srcs[0] OP ... OP srcs[n_srcs - 1], position by position, in ONE pass: every operand is read once and
+ * dst is written once (n_srcs + 2 array lengths of traffic, where a chain of pairwise calls would move 3 n_srcs).
+ *   bit filters:  OR, AND, ANDNOT (dst & ~srcs[0] & ... & ~srcs[n_srcs - 1]);
+ *   counting:     ADD = min(sum, MAX) -- it saturates at the counter's maximum and never wraps, as incrementAll leaves a
+ *                 counter (CountingBloomFilter.hpp:165-183) -- MAX, MIN; for counters of 8, 16, 32 and 64 bits.
+ * *pop_out (may be NULL) = what btlbf_popcount(dst) would return afterwards (set bits / non-zero counters), accumulated
+ * in the same pass.  dst's nEntry, tEntry, dFPR and threshold are left as they are: the library cannot know how many
+ * distinct entries the result holds (the caller has btlbf_set_n_entry).  Shards of the same range combine like whole
+ * filters.  All n_srcs + 1 filters are locked, in address order.
+ * Refused: a null argument or handle; n_srcs == 0 or > BTLBF_COMBINE_MAX_SRCS; dst among the sources; an op that does
+ * not belong to dst's kind; a source that differs from dst in kind, size, local bytes, shard range, device, hash count,
+ * k-mer size or spaced seeds (both without, or the same seed strings and h2). */
+int btlbf_combine(btlbf_filter* dst, btlbf_filter* const* srcs, unsigned n_srcs, int op, uint64_t* pop_out);
+
+/* A new filter of btlbf_size(f) / factor positions whose position p combines source positions p + j * size / factor,
+ * j < factor: by OR for a bit filter, by saturating ADD for a counting filter.  A bit filter built at m folds into, byte
+ * for byte, the filter built at m / factor from the same data; a counting filter built with BTLBF_INCREMENT_ALL into the
+ * INCREMENT_ALL filter of the smaller size.  For BTLBF_INCREMENT_MIN the folded filter is an upper bound of the smaller
+ * size's filter, counter by counter, not the same filter (incrementMin looks at the counters it shares).
+ * Hash count, k, spaced seeds, threshold, nEntry, tEntry and dFPR carry over; factor == 1 is btlbf_clone.
+ * Refused: a null argument; a shard; factor == 0; size % factor != 0; a result the constructors could not have made
+ * (above, "lifetime": size / factor bits not a multiple of 8; size / factor counters not a multiple of 8 bytes). */
+int btlbf_fold(btlbf_filter** out, btlbf_filter* f, uint64_t factor);
+
+/* From a counting filter of any width, the bit filter of btlbf_size(f) bits with bit p = (counter p >= threshold); hash
+ * count, k and spaced seeds are f's, nEntry / tEntry / dFPR are 0.  threshold == 0 means f's own.  contains() of the
+ * result equals CountingBloomFilter::contains at that threshold (CountingBloomFilter.hpp:190-196), k-mer for k-mer, in
+ * 1/8 to 1/64 of the memory -- and the result is what btlbf_screen_seqs and btlbf_mibf_create take.
+ * Refused: a null argument; a bit filter; a shard; threshold == 0 on a filter whose own threshold is 0; a counter count
+ * that is not a multiple of 8 (possible for the wide kinds). */
+int btlbf_threshold_bits(btlbf_filter** out, btlbf_filter* f, unsigned threshold);
 
 /* ---- rank structure over a bit filter (miBF stage 2) ------------------------------------
  * The reference's multi-index Bloom filter maps a set bit to an index of its ID array with

@@ -371,7 +371,43 @@ class BloomFilter
 		return m_f;
 	}
 
+	// ---- filter algebra (btlbf_combine / btlbf_fold): not in the reference, whose users loop over getFilter() ----
+	// A filter around a C-ABI handle that it owns from now on (what fold and CountingBloomFilter::toBloomFilter return)
+	struct AdoptHandle {};
+	BloomFilter(btlbf_filter* owned, AdoptHandle)
+	  : m_f(owned)
+	{}
+	// this |= other(s), this &= other(s), this &= ~other(s): filters of the same size, hash count, k and seeds; one pass over
+	// HBM whatever the number of operands (at most BTLBF_COMBINE_MAX_SRCS).  nEntry / tEntry stay as they are.
+	void merge(const BloomFilter& other) { combine({ &other }, BTLBF_COMBINE_OR); }
+	void merge(const std::vector<const BloomFilter*>& others) { combine(others, BTLBF_COMBINE_OR); }
+	void intersect(const BloomFilter& other) { combine({ &other }, BTLBF_COMBINE_AND); }
+	void intersect(const std::vector<const BloomFilter*>& others) { combine(others, BTLBF_COMBINE_AND); }
+	void subtract(const BloomFilter& other) { combine({ &other }, BTLBF_COMBINE_ANDNOT); }
+	void subtract(const std::vector<const BloomFilter*>& others) { combine(others, BTLBF_COMBINE_ANDNOT); }
+	// the filter of getFilterSize() / factor bits that the same insertions would have built (positions are hash % size,
+	// BloomFilter.hpp:190); factor must divide the size, and the result be a multiple of 8 bits
+	BloomFilter fold(uint64_t factor) const
+	{
+		flush();
+		btlbf_filter* h = nullptr;
+		btlbf_shim::check(btlbf_fold(&h, m_f, factor));
+		return BloomFilter(h, AdoptHandle{});
+	}
+
   protected:
+	void combine(const std::vector<const BloomFilter*>& others, int op)
+	{
+		flush();
+		std::vector<btlbf_filter*> hs;
+		for (const BloomFilter* o : others) {
+			o->flush();
+			hs.push_back(o->m_f);
+		}
+		btlbf_shim::check(btlbf_combine(m_f, hs.data(), (unsigned)hs.size(), op, nullptr));
+		touch();
+	}
+
 	BloomFilter(const BloomFilter&) = delete; // BloomFilter.hpp:384
 	BloomFilter& operator=(const BloomFilter&) = delete;
 

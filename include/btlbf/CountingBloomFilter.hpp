@@ -13,12 +13,14 @@
 // header does not fit T (BloomFilterSize * sizeof(T) != BloomFilterSizeInBytes), loading fails here.
 #ifndef BTLBF_COUNTINGBLOOMFILTER_HPP
 #define BTLBF_COUNTINGBLOOMFILTER_HPP
+#include "BloomFilter.hpp"
 #include "detail.hpp"
 
 #include <algorithm>
 #include <cmath>
 #include <istream>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 template<typename T>
@@ -199,7 +201,52 @@ class CountingBloomFilter
 
 	btlbf_filter* handle() const { return m_f; }
 
+	// ---- filter algebra (btlbf_combine / btlbf_fold / btlbf_threshold_bits): not in the reference ----
+	// this = this OP other(s), counter by counter, in one pass over HBM: BTLBF_COMBINE_ADD saturates at the maximum of T, as
+	// incrementAll does (:165-183), so it gives what incrementAll of all the inputs into one filter leaves;
+	// BTLBF_COMBINE_MAX, BTLBF_COMBINE_MIN.  Filters of the same size, hash count, k and seeds.
+	// (These members are templates only so that an explicit instantiation of the class -- a program that wants none of them
+	// -- does not need the algebra's entry points at link time; callers write m.merge(other), f.fold(2), c.toBloomFilter().)
+	template<typename Same = T>
+	void merge(const CountingBloomFilter<Same>& other, int op = BTLBF_COMBINE_ADD)
+	{
+		merge(std::vector<const CountingBloomFilter<Same>*>{ &other }, op);
+	}
+	template<typename Same = T>
+	void merge(const std::vector<const CountingBloomFilter<Same>*>& others, int op = BTLBF_COMBINE_ADD)
+	{
+		static_assert(std::is_same<Same, T>::value, "merge: counters of the same type");
+		std::vector<btlbf_filter*> hs;
+		for (const CountingBloomFilter<Same>* o : others)
+			hs.push_back(o->m_f);
+		btlbf_shim::check(btlbf_combine(m_f, hs.data(), (unsigned)hs.size(), op, nullptr));
+	}
+	// the filter of size() / factor counters: for counters built with incrementAll, the filter the same calls would have
+	// built at that size; for insert (= incrementMin) an upper bound of it
+	template<typename Same = T>
+	CountingBloomFilter<Same> fold(uint64_t factor) const
+	{
+		static_assert(std::is_same<Same, T>::value, "fold: counters of the same type");
+		btlbf_filter* h = nullptr;
+		btlbf_shim::check(btlbf_fold(&h, m_f, factor));
+		return CountingBloomFilter(h, m_threshold);
+	}
+	// the bit filter of the counters >= threshold (0: this filter's own): its contains() is this filter's at that
+	// threshold (:190-196), in 1 / (8 sizeof(T)) of the memory
+	template<typename Bits = BloomFilter>
+	Bits toBloomFilter(unsigned threshold = 0) const
+	{
+		btlbf_filter* h = nullptr;
+		btlbf_shim::check(btlbf_threshold_bits(&h, m_f, threshold));
+		return Bits(h, typename Bits::AdoptHandle{});
+	}
+
   private:
+	CountingBloomFilter(btlbf_filter* owned, unsigned countThreshold)
+	  : m_f(owned)
+	  , m_threshold(countThreshold)
+	{}
+
 	// the first m_hashNum values of any indexable holder as a contiguous row.  A value, not a member: the
 	// reference's per-k-mer calls may come from many threads at once (CountingBloomFilter.hpp:117-132)
 	struct Row {
