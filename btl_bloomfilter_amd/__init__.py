@@ -8,9 +8,9 @@ from . import _lib  # noqa: F401
 from .engine import (BloomFilter, KmerBloomFilter, insertSeq, CountingBloomFilter, hash_seqs, hash_kmers, sthash_seqs, synth_reads_device,  # noqa: F401
                      bits_to_bool, fastx_batches, count_per_seq, RankSupport, MIBloomFilter, interleave_mates,
                      interleave_mates_device, classify_tally, countWindows, countWindowsFile, screenSeqs, screen_tally,
-                     screenFile)
+                     screenFile, KmerCardinality, solve_spectrum)
 
 __all__ = ["BloomFilter", "KmerBloomFilter", "insertSeq", "CountingBloomFilter", "hash_seqs", "hash_kmers", "sthash_seqs", "synth_reads_device",
            "bits_to_bool", "fastx_batches", "count_per_seq", "RankSupport", "MIBloomFilter", "interleave_mates",
            "interleave_mates_device", "classify_tally", "countWindows", "countWindowsFile", "screenSeqs", "screen_tally",
-           "screenFile"]
+           "screenFile", "KmerCardinality", "solve_spectrum"]

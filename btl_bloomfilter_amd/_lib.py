@@ -24,6 +24,7 @@ SCREEN_MAX_FILTERS = 16
 COMBINE_OR, COMBINE_AND, COMBINE_ANDNOT, COMBINE_ADD, COMBINE_MAX, COMBINE_MIN = range(6)
 COMBINE_MAX_SRCS = 16
 PROF_SLOTS = 10
+CARD_SAMPLE_BITS, CARD_TABLE_BITS = 11, 22  # the defaults of the layers above the C ABI
 PROF_NAMES = ["insert_direct", "query_direct", "insert_hash", "insert_split", "insert_apply", "query_hash",
               "query_split", "query_test", "query_resolve", "other"]
 
@@ -48,6 +49,11 @@ class MibfClassifyParams(C.Structure):
 
 class ScreenParams(C.Structure):
     _fields_ = [("min_fraction", C.c_double), ("min_hits", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class CardEstimate(C.Structure):
+    _fields_ = [("distinct", C.c_double), ("singletons", C.c_double), ("occupancy", C.c_double), ("windows", C.c_uint64),
+                ("clean_windows", C.c_uint64), ("sampled", C.c_uint64), ("overflow_buckets", C.c_uint64)]
 
 
 class MibfBuildParams(C.Structure):
@@ -228,6 +234,17 @@ _PROTOS = {
     "btlbf_screen_fastx_close": (None, [_P]),
     "btlbf_screen_fastx": (C.c_int, [_P, C.c_uint, C.c_char_p, C.c_uint32, C.POINTER(ScreenParams), C.c_uint64, _P, _P, _P,
                                      C.POINTER(FastxStats)]),
+    "btlbf_card_create": (C.c_int, [C.POINTER(_P), C.c_uint, C.c_uint, C.c_uint, C.c_int]),
+    "btlbf_card_destroy": (None, [_P]),
+    "btlbf_card_clear": (C.c_int, [_P]),
+    "btlbf_card_add_seqs": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(Layout), C.c_int, _P]),
+    "btlbf_card_add_fastx": (C.c_int, [_P, C.c_char_p, C.c_uint32, C.c_uint64, C.POINTER(FastxStats)]),
+    "btlbf_card_merge": (C.c_int, [_P, _P]),
+    "btlbf_card_download": (C.c_int, [_P, _P, _P]),
+    "btlbf_card_upload": (C.c_int, [_P, _P, _P]),
+    "btlbf_card_histogram": (C.c_int, [_P, _P, C.c_uint]),
+    "btlbf_card_solve": (C.c_int, [_P, C.c_uint, C.c_uint, C.c_uint, C.POINTER(CardEstimate), _P]),
+    "btlbf_card_estimate_now": (C.c_int, [_P, C.c_uint, C.POINTER(CardEstimate), _P]),
 }
 EXPORTS = sorted(_PROTOS)
 

@@ -18,9 +18,10 @@ HEADERS = ["internal.hpp", "mibf_plan.hpp", "fastx_side.hpp", "part_plan.hpp", "
            os.path.join("..", "..", "include", "btlbf.h")]
 # host units (the C ABI over host_internal.hpp) and kernel units; tools/sanitize_host.sh reads both lists
 HOST_UNITS = ["capi", "host_io", "host_seq", "host_query", "host_partition", "host_aux", "host_mibf", "host_mibf_probs",
-              "host_mibf_fastx", "host_mibf_build", "host_screen", "host_algebra", "fastx"]
+              "host_mibf_fastx", "host_mibf_build", "host_screen", "host_algebra", "host_card", "fastx"]
 KERNEL_UNITS = ["seq_kernels", "aux_kernels", "split_query_kernels", "partition_kernels", "mibf_kernels", "mibf_classify_kernels",
-                "mibf_classify_pair_kernels", "mibf_stream_kernels", "mibf_build_kernels", "wide_counter_kernels", "screen_kernels", "algebra_kernels"]
+                "mibf_classify_pair_kernels", "mibf_stream_kernels", "mibf_build_kernels", "wide_counter_kernels", "screen_kernels", "algebra_kernels",
+                "card_kernels"]
 # (object name, source, extra flags): pass A of the partitioned pipeline is one unit per hash count
 UNITS = [(u, u + ".cpp", []) for u in HOST_UNITS] + [(u, u + ".hip", []) for u in KERNEL_UNITS]
 UNITS += [("part_hash_h%d" % h, "part_hash_inst.hip", ["-DBTLBF_PART_H=%d" % h]) for h in range(1, 9)]

@@ -120,6 +120,23 @@ struct btlbf_filter {
 	unsigned prof_calls[BTLBF_PROF_SLOTS] = {0};
 };
 
+// -------------------------------------------------------------------------------------------------
+// k-mer cardinality sketch (host_card.cpp)
+// -------------------------------------------------------------------------------------------------
+struct btlbf_card {
+	mutable std::recursive_mutex mu; // every entry point that takes the sketch holds it for its whole duration
+	unsigned k = 0, sample_bits = 0, table_bits = 0;
+	int device = 0;
+	btlbf::HashParams hp{};              // plain ntHash, one value per window
+	uint32_t* d_table = nullptr;         // 2^table_bits counters
+	uint32_t* d_wrapped = nullptr;       // a bit per counter, all zero between launches (card_kernels.hip)
+	unsigned long long* d_tot = nullptr; // totals3
+	btlbf::DevScratch hist;              // the histogram call's n_hist words
+	uint64_t counters() const { return 1ull << table_bits; }
+	uint64_t table_bytes() const { return counters() * 4; }
+	uint64_t wrapped_bytes() const { return counters() / 8; }
+};
+
 namespace btlbf {
 
 // The kinds: a bit filter, or counters of 1, 2, 4 or 8 bytes (CountingBloomFilter<T>).  Bytes per counter of a kind:

@@ -529,4 +529,28 @@ hipError_t launch_fold(int counter_bytes, const void* src, uint64_t stride, uint
 hipError_t launch_threshold_bits(int counter_bytes, const void* src, uint64_t src_bytes, uint64_t threshold, void* out,
                                  uint64_t out_words, hipStream_t s);
 
+// the k-mer cardinality sketch (card_kernels.hip; the definition is in include/btlbf.h): 2^table_bits uint32_t counters
+// that saturate, a bit per counter (`wrapped`: 2^table_bits / 32 words, all zero between launches) in which the fused
+// kernel marks a counter it carried past 2^32 - 1 and from which the launcher's second kernel restores the maximum
+struct CardArgs {
+	const uint8_t* seq; // device
+	uint64_t len;
+	LayoutParams layout;
+	HashParams hp; // plain ntHash, h = 1
+	uint32_t* table;
+	uint32_t* wrapped;
+	uint32_t table_bits, sample_bits;
+	unsigned long long* totals3; // += {windows, clean windows, sampled windows}
+	uint64_t n_tiles, tiles_per_block;
+};
+static constexpr uint32_t kCardMinTableBits = 6, kCardMaxTableBits = 28, kCardMaxSampleBits = 32;
+static constexpr uint32_t kCardMinHist = 3, kCardMaxHist = 8192;
+hipError_t launch_card(const CardArgs& a, hipStream_t s);
+// t[min(table[i], n_hist - 1)] += 1 over the 2^table_bits counters (the caller zeroes t)
+hipError_t launch_card_hist(const uint32_t* table, uint32_t table_bits, uint32_t n_hist, unsigned long long* t,
+                            hipStream_t s);
+// dst[i] = min(dst[i] + src[i], 2^32 - 1); dst_totals3 += src_totals3
+hipError_t launch_card_merge(uint32_t* dst, const uint32_t* src, uint32_t table_bits, unsigned long long* dst_totals3,
+                             const unsigned long long* src_totals3, hipStream_t s);
+
 } // namespace btlbf

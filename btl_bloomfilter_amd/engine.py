@@ -1257,3 +1257,107 @@ class _ScreenFile(_Owned):
         check(self._L.btlbf_screen_fastx_tally(self._h, C.c_void_p(passed.ctypes.data), C.c_void_p(best.ctypes.data),
                                                C.c_void_p(totals.ctypes.data)))
         return passed, best, totals
+
+
+class CardinalityEstimate:
+    """what KmerCardinality.estimate and solve_spectrum return: distinct (F0), singletons (f1), occupancy (the share of
+    the table's counters that are not zero), spectrum (numpy: spectrum[i - 1] = f_i, the distinct k-mers seen i times,
+    i = 1 .. n_hist - 2), overflow_buckets, and -- from a sketch -- windows, clean_windows, sampled"""
+
+    def __init__(self, est, f):
+        for name, _ in est._fields_:
+            setattr(self, name, getattr(est, name))
+        self.spectrum = np.array(f[1:], np.float64)
+
+    def at_least(self, T):
+        """the distinct k-mers seen at least T times: distinct - (f_1 + ... + f_{T-1}); what a filter that takes the
+        output of CountingBloomFilter.toBloomFilter(T) has to hold"""
+        T = int(T)
+        if T < 1 or T - 1 > self.spectrum.size:
+            raise ValueError("at_least(T): T must be 1..%d for this spectrum" % (self.spectrum.size + 1))
+        return float(self.distinct - self.spectrum[: T - 1].sum())
+
+    def __repr__(self):
+        return "CardinalityEstimate(distinct=%.6g, singletons=%.6g, occupancy=%.4f)" % (self.distinct, self.singletons,
+                                                                                        self.occupancy)
+
+
+def solve_spectrum(t, sample_bits, table_bits):
+    """the estimate from a histogram t of a sketch's counters (t[i] counters equal to i, the last entry those at or above
+    it; KmerCardinality.histogram): btlbf_card_solve, host arithmetic that needs no GPU"""
+    t = np.ascontiguousarray(t, np.uint64)
+    est = _lib.CardEstimate()
+    f = np.zeros(max(t.size - 1, 1), np.float64)
+    check(_lib.load().btlbf_card_solve(C.c_void_p(t.ctypes.data), t.size, int(sample_bits), int(table_bits), C.byref(est),
+                                       C.c_void_p(f.ctypes.data)))
+    return CardinalityEstimate(est, f)
+
+
+class KmerCardinality(_Owned):
+    """A sampled, bucketed k-mer sketch in HBM (btlbf_card_*): estimates the distinct k-mers of reads and how many of
+    them occur once, twice, ... -- the numbers the filters above are sized from -- in one pass of a fused kernel.
+    A window is sampled when the top sample_bits bits of its mixed canonical ntHash value are zero; a sampled window
+    counts in one of 2^table_bits saturating 32-bit counters."""
+
+    _destroy = "btlbf_card_destroy"
+
+    def __init__(self, k, sample_bits=_lib.CARD_SAMPLE_BITS, table_bits=_lib.CARD_TABLE_BITS, device=0):
+        self._L = _lib.load()
+        self.k, self.sample_bits, self.table_bits, self.device = int(k), int(sample_bits), int(table_bits), int(device)
+        h = C.c_void_p()
+        check(self._L.btlbf_card_create(C.byref(h), self.k, self.sample_bits, self.table_bits, self.device))
+        self._h = h
+
+    def clear(self):
+        check(self._L.btlbf_card_clear(self._h))
+
+    def addSeqs(self, seq, starts=None, read_len=0, stream=None):
+        """add the windows of a buffer (layouts, memory spaces and streams as BloomFilter.insertSeqs); calls accumulate"""
+        b = _Buf(seq)
+        lay, keep = _layout(starts, read_len, b.mem)
+        check(self._L.btlbf_card_add_seqs(self._h, b.ptr, b.nbytes, C.byref(lay) if lay else None, b.mem,
+                                          _stream_ptr(stream, b.keep)))
+
+    def addFile(self, path, per_line=False, batch_bytes=0):
+        """add the windows of a FASTA / FASTQ file, plain or gzip -> the call's statistics (n_windows = clean windows,
+        n_hits = sampled windows)"""
+        st = _lib.FastxStats()
+        check(self._L.btlbf_card_add_fastx(self._h, str(path).encode(), _lib.FASTX_LINES if per_line else 0,
+                                           int(batch_bytes), C.byref(st)))
+        return st.as_dict()
+
+    def merge(self, other):
+        """add another sketch of the same k, sample_bits, table_bits and device: the sketch of both inputs"""
+        check(self._L.btlbf_card_merge(self._h, other._h))
+        return self
+
+    def _download(self):
+        table, totals = np.zeros(1 << self.table_bits, np.uint32), np.zeros(3, np.uint64)
+        check(self._L.btlbf_card_download(self._h, C.c_void_p(table.ctypes.data), C.c_void_p(totals.ctypes.data)))
+        return table, totals
+
+    def table(self):
+        return self._download()[0]
+
+    def totals(self):
+        """(windows, clean windows, sampled windows)"""
+        return tuple(int(x) for x in self._download()[1])
+
+    def upload(self, table, totals):
+        table = np.ascontiguousarray(table, np.uint32)
+        totals = np.ascontiguousarray(totals, np.uint64)
+        if table.size != 1 << self.table_bits or totals.size != 3:
+            raise ValueError("upload: a table of 2^%d counters and 3 totals" % self.table_bits)
+        check(self._L.btlbf_card_upload(self._h, C.c_void_p(table.ctypes.data), C.c_void_p(totals.ctypes.data)))
+
+    def histogram(self, n_hist):
+        """t[i] = counters equal to i (i < n_hist - 1), t[n_hist - 1] = counters at or above n_hist - 1"""
+        t = np.zeros(max(int(n_hist), 1), np.uint64)
+        check(self._L.btlbf_card_histogram(self._h, C.c_void_p(t.ctypes.data), int(n_hist)))
+        return t
+
+    def estimate(self, n_hist=64):
+        est = _lib.CardEstimate()
+        f = np.zeros(max(int(n_hist) - 1, 1), np.float64)
+        check(self._L.btlbf_card_estimate_now(self._h, int(n_hist), C.byref(est), C.c_void_p(f.ctypes.data)))
+        return CardinalityEstimate(est, f)

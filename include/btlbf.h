@@ -1013,6 +1013,75 @@ int btlbf_screen_fastx(btlbf_filter* const* filters, unsigned n_filters, const c
                        const btlbf_screen_params* p, uint64_t batch_bytes, uint64_t* passed, uint64_t* best,
                        uint64_t* totals4, btlbf_fastx_stats* stats);
 
+/* ---- k-mer cardinality and spectrum: how large must the filter be? ---------------------------------------------
+ * Every constructor above takes a size; this estimates the number it is computed from -- F0, the distinct k-mers of the
+ * input, and f1, f2, ..., the distinct k-mers that occur once, twice, ... -- from a sampled, bucketed sketch built in
+ * HBM by one fused kernel (csrc/card_kernels.hip) and solved on the host.
+ * THE SKETCH (tests hold the code to it bit for bit).  For every clean window w of the input (clean as everywhere in
+ * this header): h0(w) = the canonical ntHash value (btlbf_hash_seqs with hash_num 1, no seeds); z = mix64(h0), mix64 the
+ * splitmix64 finaliser written out at btlbf_digest (h0 = min(forward, reverse) is not uniform in its high bits);
+ * w is SAMPLED iff sample_bits == 0 || (z >> (64 - sample_bits)) == 0; a sampled window adds 1 to
+ * table[z & (2^table_bits - 1)].  The counters are uint32_t and saturate at 2^32 - 1: they never wrap.
+ * totals3 = {windows, clean windows, sampled windows} (a window: k bytes inside one sequence, as
+ * btlbf_count_windows_seqs counts them), accumulated on the device.
+ *   sample_bits 0..32, table_bits 6..28 (the table takes 4 << table_bits bytes of HBM, plus a bit per counter),
+ *   kmer_size 1..32768 (what btlbf_hash_seqs takes without seeds).  Spaced seeds are not offered.
+ * create / destroy / clear : a sketch on `device`, all zero.  clear zeroes the table and the totals.
+ * add_seqs : the windows of a buffer (layout, mem and stream as btlbf_insert_seqs) are added: BTLBF_HOST stages the
+ *   buffer and returns with the work finished; BTLBF_DEVICE runs on the caller's stream and returns with the work
+ *   queued.  Calls accumulate: two calls over two halves of a set of reads leave what one call over all leaves.
+ * add_fastx : the same over a FASTA / FASTQ file, plain or gzip, in the file classifier's arrangement: one sequential
+ *   parser (btlbf_fastx_open / _next) on a thread of its own, parser batches of batch_bytes (0 = 64 MiB, or what the
+ *   test switch BTLBF_FASTX_DEV_BYTES says) that rotate through two device slots, the copy of batch j + 1 overlapping
+ *   the kernel of batch j.  flags: BTLBF_FASTX_LINES, BTLBF_FASTX_PAGEABLE, BTLBF_FASTX_WHOLE.  Without
+ *   BTLBF_FASTX_WHOLE a record that does not fit the rest of a batch is cut with the parser's k - 1 base overlap, so
+ *   that every window is counted exactly once: the sketch does not depend on batch_bytes.  stats (optional):
+ *   n_records, n_bases, n_batches, n_windows = clean windows and n_hits = sampled windows of this call, the seconds.
+ *   Returns with the work finished.  A parser error (BTLBF_EIO for a truncated gzip stream) comes back unchanged; the
+ *   batches before it stay added.
+ * merge : dst[i] = min(dst[i] + src[i], 2^32 - 1) and the totals added; both of the same kmer_size, sample_bits,
+ *   table_bits and device, else BTLBF_EINVAL.  The sketch of two inputs merged is the sketch of their concatenation.
+ * download / upload : the 2^table_bits counters and totals3, to and from host memory (a sketch can be kept, or moved
+ *   between GPUs and merged there).
+ * histogram : t[i] = the number of counters equal to i for i < n_hist - 1, t[n_hist - 1] = those >= n_hist - 1;
+ *   n_hist 3..8192; t is host memory.  One streaming pass over the table.
+ * clear, merge, download, upload, histogram and estimate_now take no stream: they wait for ALL streams of the device
+ * before they look at the table, and return with their work finished.
+ * solve : pure host arithmetic, no HIP call, no GPU.  In double, in this order:  R = 2^table_bits;
+ *   L = table_bits * log(2.0) - log((double)t[0]);  F0 = ldexp(L, table_bits + sample_bits);
+ *   phi[i] = t[i] / (t[0] * L) - (sum_{j=1}^{i-1} j * t[i-j] * phi[j]) / (i * t[0])  for i = 1 .. n_hist - 2;
+ *   f[i] = fabs(phi[i]) * F0;  f[0] = 0.  f holds n_hist - 1 doubles.  est->distinct = F0, singletons = f[1],
+ *   occupancy = 1 - t[0] / R, overflow_buckets = t[n_hist - 1]; windows, clean_windows and sampled are 0 (estimate_now
+ *   fills them from totals3).  t[0] == 0 (the table is full) is BTLBF_EINVAL -- raise table_bits or sample_bits -- and
+ *   so is a histogram that does not sum to R; nothing is written then.  t[0] == R: F0 = 0 and every f is 0.
+ *   Trust the estimate while the occupancy is roughly between 0.05 and 0.8; no limit is
+ *   enforced.
+ * estimate_now : histogram + solve.
+ * Refused before any HIP call, with nothing allocated and no output written: a null argument (layout, stream and stats
+ * may be null; seq when len == 0); kmer_size 0 or above 32768; sample_bits > 32; table_bits outside 6..28; n_hist outside
+ * 3..8192; a mem that is neither space; a len that is no multiple of read_len (all BTLBF_EINVAL); an unreadable path
+ * (BTLBF_EIO).  A call that returns BTLBF_OK has written every element of every output. */
+typedef struct btlbf_card btlbf_card;
+typedef struct btlbf_card_estimate {
+	double distinct;   /* F0 */
+	double singletons; /* f1 */
+	double occupancy;  /* 1 - t[0] / 2^table_bits */
+	uint64_t windows, clean_windows, sampled; /* totals3 (0 from btlbf_card_solve) */
+	uint64_t overflow_buckets;                /* t[n_hist - 1] */
+} btlbf_card_estimate;
+int btlbf_card_create(btlbf_card** out, unsigned kmer_size, unsigned sample_bits, unsigned table_bits, int device);
+void btlbf_card_destroy(btlbf_card* c);
+int btlbf_card_clear(btlbf_card* c);
+int btlbf_card_add_seqs(btlbf_card* c, const char* seq, uint64_t len, const btlbf_layout* layout, int mem, void* stream);
+int btlbf_card_add_fastx(btlbf_card* c, const char* path, uint32_t flags, uint64_t batch_bytes, btlbf_fastx_stats* stats);
+int btlbf_card_merge(btlbf_card* dst, const btlbf_card* src);
+int btlbf_card_download(btlbf_card* c, uint32_t* table, uint64_t* totals3);
+int btlbf_card_upload(btlbf_card* c, const uint32_t* table, const uint64_t* totals3);
+int btlbf_card_histogram(btlbf_card* c, uint64_t* t, unsigned n_hist);
+int btlbf_card_solve(const uint64_t* t, unsigned n_hist, unsigned sample_bits, unsigned table_bits,
+                     btlbf_card_estimate* est, double* f);
+int btlbf_card_estimate_now(btlbf_card* c, unsigned n_hist, btlbf_card_estimate* est, double* f);
+
 #ifdef __cplusplus
 }
 #endif
